@@ -12,13 +12,20 @@ Inputs are synthetic (uniform[-1,1), seed = global channel id), generated on
 the device and resident in HBM before timing.  Channels are independent: ranks
 process disjoint channel shards with no collective in the timed region.
 
-Also measured (same JSON line): the roofline of the dominant kernel (HIP events
-on the launch stream), config 2 (65536 x 1024 c2c f32 FFT) and config 4 (FIR
-overlap-save 257 taps, 8 ch x 2^24) GB/s, and the reference's own CPU STFT
-(oracle/_ref, i.e. the reference sources compiled in the build container) timed
-on this host's cores on a bounded sample.
+A plain run sets up, warms up, times the K steps and prints the result line
+(with the roofline of the dominant kernel from HIP events around the timed
+launches themselves).  `--dump-outputs DIR` also writes a fixed, seeded sample
+of the last timed step's magnitude rows to DIR as float32 .npy.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]     (N > 1: one process drives N GPUs)
+With `--full` the same JSON line also carries: the check of sampled rows
+against NumPy f64, config 2 (65536 x 1024 c2c f32 FFT) and config 4 (FIR
+overlap-save 257 taps, 8 ch x 2^24) GB/s, config 3, the per-GPU shard, the
+reference's other STFT sizes and the feature legs, and the reference's own CPU
+STFT (oracle/_ref, i.e. the reference sources compiled in the build container)
+timed on this host's cores on a bounded sample.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                             (N > 1: one process drives N GPUs)
     torchrun --nproc-per-node N bench.py --gpus N ...        (one rank per GPU)
 Both N > 1 forms run through the library's plain-C RCCL layer
 (include/vv_dsp/vv_dsp_dist.h): ncclCommInitAll in one process, or
@@ -58,6 +65,9 @@ TRAFFIC_JSON = (sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_ben
                        key=lambda f: (os.path.basename(f)[:3], "_final_" in f)) or
                 [os.path.join(ROOT, "profiles", "r01_bench_pmc.json")])[-1]
 METRIC = "STFT frames/sec (1024-pt, hop 256) at 1/2/4/8 GPU; achieved HBM GB/s vs peak"
+DUMP_NAME = "stft_magnitude_rows"   # --dump-outputs: DIR/stft_magnitude_rows.npy, float32 [rows][1024]
+DUMP_ROWS = 8192                    # 32 MB of the 118 GB output
+DUMP_SEED = 5
 TIMING_NOTE = ("ms_avg: HIP events around the timed launches back to back / launches (the launch stream); "
                "ms_avg_isolated / ms_min: an event pair around each single launch")
 
@@ -579,8 +589,17 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=25)
     ap.add_argument("--channels", type=int, default=CH_TOTAL,
                     help="channels of the whole job (config 5: 256), split over the ranks (strong scaling)")
-    ap.add_argument("--no-extras", action="store_true", help="skip config 2/3/4, shard and CPU baseline legs")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check sampled rows against NumPy f64 and run the extra legs "
+                         "(--legs) and the CPU baseline; off by default: a plain run only times the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write a fixed, seeded sample of the last step's magnitude rows "
+                         f"(at most {DUMP_ROWS} rows of 1024 f32, the same rows on every run of the same job) "
+                         f"to DIR/{DUMP_NAME}.npy")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip config 2/3/4, shard and CPU baseline legs")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="with --full: skip the CPU baseline leg (profiling runs)")
     ap.add_argument("--legs", default="c2c,fir,config3,shard,sizes,features",
                     help="extra GPU legs: c2c (config 2), fir (config 4), config3, shard (config 5's 32-channel "
                          "per-GPU shard of the N = 8 run), sizes (the reference's STFT sizes 256/512/2048/4096 on "
@@ -654,7 +673,7 @@ def result_line(args, value, world, elapsed, total_ch, per_gpu, nfr, parallelism
             "output": "[ch][frame][1024] f32 magnitudes (stft.c:133-139)",
             "parallelism": parallelism},
         "roofline": roofline,
-        "check_row_vs_numpy_f64": bool(ok),
+        "check_row_vs_numpy_f64": None if ok is None else bool(ok),   # checked with --full
     }
 
 
@@ -671,6 +690,34 @@ def check_rows(sig, out, channels):
         x0 = sig[c, fr * HOP: fr * HOP + NFFT].double().cpu().numpy()
         ok = ok and np.allclose(out[c, fr].cpu().numpy(), np.abs(np.fft.fft(x0 * hann64())), rtol=5e-5, atol=5e-5)
     return ok
+
+
+def dump_row_ids(total_ch, nfr, rows=DUMP_ROWS):
+    """The rows --dump-outputs writes, as sorted global row numbers (channel * nfr + frame): every row of a
+    job of at most `rows` rows; otherwise the first two and last two frames (the zero-padded tail) of the
+    first and last channel and a seeded draw over all rows -- a function of the job's shape alone."""
+    total = total_ch * nfr
+    if total <= rows:
+        return np.arange(total, dtype=np.int64)
+    edge = np.unique([c * nfr + f for c in (0, total_ch - 1) for f in (0, 1, nfr - 2, nfr - 1)]).astype(np.int64)
+    pick = np.random.default_rng(DUMP_SEED).choice(total, size=rows, replace=False).astype(np.int64)
+    pick = pick[~np.isin(pick, edge)][:rows - len(edge)]
+    return np.sort(np.concatenate([edge, pick]))
+
+
+def dump_rows(dirname, shards, total_ch, nfr, suffix=""):
+    """Write the sampled rows held by `shards` -- (first channel, [ch][frame][1024] device tensor) in channel
+    order -- as float32 [rows][1024] to dirname/DUMP_NAME<suffix>.npy."""
+    ids = dump_row_ids(total_ch, nfr)
+    parts = [np.empty((0, NFFT), np.float32)]
+    for lo, out in shards:
+        mine = ids[(ids >= lo * nfr) & (ids < (lo + out.shape[0]) * nfr)] - lo * nfr
+        with torch.cuda.device(out.device):
+            sel = torch.from_numpy(mine).to(out.device)
+            parts.append(out.reshape(-1, NFFT).index_select(0, sel).cpu().numpy())
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, DUMP_NAME + suffix + ".npy"),
+            np.ascontiguousarray(np.concatenate(parts), dtype=np.float32))
 
 
 def main_plain(args):
@@ -712,7 +759,9 @@ def main_plain(args):
     bytes_per_launch = C_ * SAMPLES * 4 + C_ * nfr * NFFT * 4 + NFFT * 4
     achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
     traffic, traffic_src = hbm_traffic(C_)
-    ok = check_rows(sig, out, (0, C_ - 1))
+    if args.dump_outputs:
+        dump_rows(args.dump_outputs, [(0, out)], total_ch, nfr)
+    ok = check_rows(sig, out, (0, C_ - 1)) if args.full else None
     del sig, out, st
     torch.cuda.empty_cache()
 
@@ -724,7 +773,8 @@ def main_plain(args):
     res = result_line(args, value, 1, elapsed, total_ch, C_, nfr,
                       "dp1 (channel shards, no data-path collective)", roof, ok)
     legs = set(args.legs.split(","))
-    if not args.no_extras:
+    extras = args.full and not args.no_extras
+    if extras:
         if "shard" in legs:
             res["config5_shard_32ch"] = shard_leg()
             torch.cuda.empty_cache()
@@ -745,7 +795,7 @@ def main_plain(args):
             except Exception as e:   # noqa: BLE001
                 res["features"] = {"error": repr(e)[:200]}
             torch.cuda.empty_cache()
-    if not args.no_extras and not args.no_cpu:
+    if extras and not args.no_cpu:
         res["cpu_baseline"] = cpu_baseline()
     print(json.dumps(res), flush=True)
 
@@ -867,11 +917,16 @@ def main_dist(args, mode, world):
 
     frames_per_step = total_ch * nfr
     value = frames_per_step * args.steps / elapsed
-    ok = all(check_rows(x["sig"], x["out"], (0, x["cnt"] - 1)) for x in slots if x["cnt"])
-    if mode == "ranks":
-        t = torch.tensor([1.0 if ok else 0.0])
-        dist.all_reduce(t, op=dist.ReduceOp.MIN)
-        ok = bool(t.item() > 0.5)
+    if args.dump_outputs:   # one file from the process that drives every GPU; under torchrun one per rank
+        dump_rows(args.dump_outputs, [(x["lo"], x["out"]) for x in slots if x["cnt"]], total_ch, nfr,
+                  suffix=f".rank{rank0}" if mode == "ranks" else "")
+    ok = None
+    if args.full:
+        ok = all(check_rows(x["sig"], x["out"], (0, x["cnt"] - 1)) for x in slots if x["cnt"])
+        if mode == "ranks":
+            t = torch.tensor([1.0 if ok else 0.0])
+            dist.all_reduce(t, op=dist.ReduceOp.MIN)
+            ok = bool(t.item() > 0.5)
 
     gather = None
     if want_gather:

@@ -20,7 +20,8 @@ def _bench(args):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--channels", "8", "--steps", "2",
-                        "--warmup", "1", "--no-extras"] + args, env=env, cwd=ROOT, capture_output=True, text=True,
+                        "--warmup", "1", "--full", "--no-extras"] + args, env=env, cwd=ROOT, capture_output=True,
+                       text=True,
                        timeout=240)
     assert p.returncode == 0, p.stderr[-2000:]
     return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
