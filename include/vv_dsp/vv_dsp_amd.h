@@ -15,6 +15,7 @@
 #include "vv_dsp/spectral/czt.h"
 #include "vv_dsp/envelope/cepstrum.h"
 #include "vv_dsp/envelope/minphase.h"
+#include "vv_dsp/resample/resampler.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -140,6 +141,24 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_fir_apply_direct_device(vv_dsp_fir_plan* p
 VV_DSP_NODISCARD vv_dsp_status vv_dsp_filtfilt_fir_device(vv_dsp_fir_plan* p, const vv_dsp_real* d_x,
                                                           vv_dsp_real* d_y, size_t n, size_t nch, size_t x_stride,
                                                           size_t y_stride, void* stream);
+
+/* Rational resampler (vv_dsp/resample/resampler.h) on device rows.
+ * _output_length: the reference's floor((in_n - 1) * ratio) + 1 in f64 with
+ * ratio = (double)num / (double)den; 0 for in_n == 0 or a NULL plan.
+ * _process_device: nch rows of in_n samples, in_stride floats apart, into rows
+ * out_stride floats apart, one launch on `stream`; *out_n (may be NULL) receives
+ * the row length.  Checks as vv_dsp_resampler_process_real, then
+ * VV_DSP_ERROR_INVALID_SIZE for in_n >= 2^31 (the reference's centre index is
+ * an int).  No alignment of pointers or strides is required.  Linear rows are
+ * bit-identical to the reference; sinc rows come from the polyphase table
+ * kernel, or from the per-output f64 kernel when the table of the reduced
+ * ratio is too large for LDS (vvhip_debug_get("STAT_RESAMPLE_TABLE") /
+ * ("STAT_RESAMPLE_GENERIC") count which ran). */
+size_t vv_dsp_resampler_output_length(const vv_dsp_resampler* rs, size_t in_n);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_resampler_process_device(vv_dsp_resampler* rs, const vv_dsp_real* d_in,
+                                                               size_t in_n, size_t nch, size_t in_stride,
+                                                               vv_dsp_real* d_out, size_t out_cap, size_t out_stride,
+                                                               void* stream, size_t* out_n);
 
 /* Hilbert analytic signal of `batch` contiguous real[N] rows -> cpx[batch][N] */
 VV_DSP_NODISCARD vv_dsp_status vv_dsp_hilbert_analytic_device(const vv_dsp_real* d_x, size_t N, size_t batch,

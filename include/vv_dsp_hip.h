@@ -58,7 +58,8 @@ const char* vvhip_last_error(void);
  *       path counter to 0);
  *   vvhip_debug_get(name)  a knob's value (-1 unset) or a path counter
  *       ("STAT_STFT_DYN", "STAT_FIR_DYN", "STAT_FIR_STATIC", "STAT_MEL_FUSED",
- *       "STAT_MEL_SPLIT": launches of that path since the last clear); -2 unknown.
+ *       "STAT_MEL_SPLIT", "STAT_RESAMPLE_TABLE", "STAT_RESAMPLE_GENERIC": launches
+ *       of that path since the last clear); -2 unknown.
  * The environment is read once per process, and only with VVHIP_AB=1 set. */
 int vvhip_debug_set(const char* name, long long value);
 int vvhip_debug_clear(const char* name);
@@ -192,6 +193,40 @@ int vvhip_fir_filtfilt_device(vvhip_fir* f, const float* d_x, float* d_y, size_t
                               size_t y_stride, void* stream);
 int vvhip_fir_filtfilt_host(vvhip_fir* f, const float* x, float* y, size_t n);
 size_t vvhip_fir_block_size(vvhip_fir* f, size_t n);
+
+/* ---- Rational resampler (src/resample/resampler.c:65-119) ----
+ * ratio = (double)num / (double)den and cutoff = fmin(1, ratio) as the reference
+ * forms them.  Rows of in_n samples in_stride floats apart -> rows of out_n
+ * samples out_stride floats apart, one launch; no alignment required.
+ *
+ * vvhip_resample_table_host (csrc/host/resampler.c; host arithmetic, no device):
+ * the polyphase table of num/den reduced by their gcd, P = num / gcd.  Row p < P:
+ * the reference's weights sinc_fn(t * cutoff) * hann(m, taps) at t = (m - taps/2) - p/P
+ * (sinc rounded to f32 first, Hann indexed by the tap), divided by the row's sum,
+ * all in f64, rounded to f32 once; row P: the same at fractional position 1
+ * (where the reference's f64 quotient falls one ulp below an integer; the table
+ * kernel evaluates those few outputs with the reference's own f64 loop, since
+ * with 4 taps and cutoff 1 their value hangs on that ulp -- DESIGN.md section 4).
+ * taps is clamped to >= 4 and raised to even as at processing time.  *phases =
+ * P + 1, *taps_eff = the row length; out (may be NULL to ask for the sizes)
+ * receives phases * taps_eff floats.
+ * vvhip_resample_run_length: outputs of one row per workgroup of the table kernel
+ * for this ratio and tap count; 0 when the table does not fit and the per-output
+ * f64 kernel runs instead.
+ * vvhip_resample_sinc_device: d_table = the table above on the stream's device
+ * (table kernel), or NULL (generic kernel); knob RESAMPLE_GENERIC = 1 forces
+ * the generic kernel. */
+int vvhip_resample_table_host(unsigned num, unsigned den, unsigned taps, float* out, size_t* phases,
+                              unsigned* taps_eff);
+size_t vvhip_resample_run_length(unsigned num, unsigned den, unsigned taps);
+/* the packed table [phases][taps] onto the current device in the table kernel's
+ * padded row layout; release with vvhip_free */
+int vvhip_resample_table_upload(const float* table, size_t phases, unsigned taps, float** d_table);
+int vvhip_resample_linear_device(const float* d_in, size_t in_n, size_t nch, size_t in_stride, float* d_out,
+                                 size_t out_n, size_t out_stride, double ratio, void* stream);
+int vvhip_resample_sinc_device(const float* d_in, size_t in_n, size_t nch, size_t in_stride, float* d_out,
+                               size_t out_n, size_t out_stride, double ratio, double cutoff, unsigned taps,
+                               const float* d_table, size_t phases, void* stream);
 
 /* ---- Hilbert analytic signal (hilbert.c:14-75) ---- */
 int vvhip_hilbert_host(const float* x, size_t n, float* z_out);

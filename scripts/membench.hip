@@ -484,3 +484,41 @@ extern "C" int membench_wprobe(const float* in, float* out, long long items, int
 #undef L
     return (int)hipGetLastError();
 }
+
+// ---- streaming at an arbitrary read:write mix (scripts/resamplebench.py) -------
+// n_in4 float4 read and n_out4 float4 written, interleaved in proportion over
+// L = max(n_in4, n_out4) grid-stride steps: step i reads in[floor(i rin)] when
+// that index advances at i, and stores to out[floor(i rout)] likewise (one of
+// the two advances at every step).  The resampler's bytes with none of its work.
+__global__ void __launch_bounds__(256) k_rwmix(const vf4* __restrict__ in, vf4* __restrict__ out, long long n_in4,
+                                               long long n_out4, long long L, double rin, double rout) {
+    constexpr int U = 4;   // steps whose loads are issued before any store
+    const long long stride = (long long)gridDim.x * 256;
+    vf4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (long long i0 = (long long)blockIdx.x * 256 + threadIdx.x; i0 < L; i0 += stride * U) {
+        vf4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long i = i0 + u * stride;
+            const long long a0 = (long long)((double)i * rin), a1 = (long long)((double)(i + 1) * rin);
+            v[u] = vf4{0.f, 0.f, 0.f, 0.f};
+            if (i < L && a1 > a0 && a0 < n_in4) v[u] = __builtin_nontemporal_load(in + a0);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long i = i0 + u * stride;
+            const long long b0 = (long long)((double)i * rout), b1 = (long long)((double)(i + 1) * rout);
+            acc += v[u];   // summed: every load stays live
+            if (i < L && b1 > b0 && b0 < n_out4) __builtin_nontemporal_store(acc, out + b0);
+        }
+    }
+}
+
+extern "C" int membench_rwmix(const float* in, float* out, long long n_in4, long long n_out4, int blocks,
+                              void* stream) {
+    const long long L = n_in4 > n_out4 ? n_in4 : n_out4;
+    if (L <= 0 || blocks <= 0) return -1;
+    hipLaunchKernelGGL(k_rwmix, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const vf4*)in, (vf4*)out, n_in4,
+                       n_out4, L, (double)n_in4 / (double)L, (double)n_out4 / (double)L);
+    return (int)hipGetLastError();
+}

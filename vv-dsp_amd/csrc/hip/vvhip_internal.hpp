@@ -18,11 +18,11 @@ enum Knob : int {
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
-    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_COUNT
+    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_COUNT
 };
 long long knob(Knob k, long long dflt);
 // launches of the paths the tests must see taken (vvhip_debug_get("STAT_..."))
-enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_COUNT };
+enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_COUNT };
 void stat_inc(Stat s);
 
 // Device-resident W_N^k = exp(-2*pi*i*k/N) table, k < N, f32 rounded from double.
@@ -216,6 +216,29 @@ hipError_t launch_fir_long_scatter(const float2* z, float* y, long long n, long 
                                    hipStream_t s);
 hipError_t launch_scale_real(float* p, long long count, float s, hipStream_t st);
 hipError_t launch_scale_cpx(float2* p, long long count, float s, hipStream_t st);
+
+// ---- rational resampler (resample_kernels.hip), resampler.c:65-119 per row ----
+// rows of in_n samples in_stride floats apart -> rows of out_n samples out_stride
+// floats apart; ratio = (double)num / (double)den as the reference forms it.
+hipError_t launch_resample_linear(const float* in, long long in_n, long long nch, long long in_stride, float* out,
+                                  long long out_n, long long out_stride, double ratio, hipStream_t s);
+// table kernel: W [phases][resample_row_stride(taps)] polyphase rows (phases = P + 1);
+// a workgroup takes resample_run(...) consecutive outputs of one row.
+constexpr int RESAMPLE_RUN = 1024;                     // outputs per workgroup, at most
+constexpr size_t RESAMPLE_LDS_BYTES = 128u << 10;      // table + input span of one workgroup
+constexpr size_t RESAMPLE_TABLE_BYTES = 96u << 10;     // larger tables take the generic kernel
+// floats from one table row to the next in LDS: taps rounded up to a multiple of 4
+// with an odd quarter, so 16 lanes' 16 B reads of 16 rows cover 16 distinct 4-bank blocks
+constexpr int resample_row_stride(int taps) { return ((taps + 3) / 4) % 2 ? (taps + 3) / 4 * 4 : (taps + 3) / 4 * 4 + 4; }
+// outputs per workgroup for this ratio and table (the span must fit beside the table); 0: generic kernel
+int resample_run(long long phases, int taps, double ratio);
+hipError_t launch_resample_table(const float* in, long long in_n, long long nch, long long in_stride, float* out,
+                                 long long out_n, long long out_stride, double ratio, double cutoff, long long phases,
+                                 int taps, const float* W, hipStream_t s);
+// every output evaluates its own weights in f64 (any ratio; slow)
+hipError_t launch_resample_generic(const float* in, long long in_n, long long nch, long long in_stride, float* out,
+                                   long long out_n, long long out_stride, double ratio, double cutoff, int taps,
+                                   hipStream_t s);
 
 // ---- DCT / Hilbert helpers (spectral_kernels.hip) ----------------------
 // single-pass analytic signal / DCT-II (analytic_kernels.hip): rows [batch][n]

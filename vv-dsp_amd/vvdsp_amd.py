@@ -72,6 +72,17 @@ def lib():
     L.vv_dsp_fir_apply_fft_device.argtypes = [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]
     L.vv_dsp_fir_apply_direct_device.argtypes = [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]
     L.vv_dsp_filtfilt_fir_device.argtypes = [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]
+    L.vv_dsp_resampler_create.argtypes = [C.c_uint, C.c_uint]
+    L.vv_dsp_resampler_create.restype = _vp
+    L.vv_dsp_resampler_destroy.argtypes = [_vp]
+    L.vv_dsp_resampler_destroy.restype = None
+    L.vv_dsp_resampler_set_ratio.argtypes = [_vp, C.c_uint, C.c_uint]
+    L.vv_dsp_resampler_set_quality.argtypes = [_vp, C.c_int, C.c_uint]
+    L.vv_dsp_resampler_output_length.argtypes = [_vp, _sz]
+    L.vv_dsp_resampler_output_length.restype = _sz
+    L.vv_dsp_resampler_process_device.argtypes = [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _sz, _vp, C.POINTER(_sz)]
+    L.vvhip_resample_run_length.argtypes = [C.c_uint, C.c_uint, C.c_uint]
+    L.vvhip_resample_run_length.restype = _sz
     L.vv_dsp_hilbert_analytic_device.argtypes = [_vp, _sz, _sz, _vp, _vp]
     L.vv_dsp_dct_make_plan.argtypes = [_sz, C.c_int, C.c_int, C.POINTER(_vp)]
     L.vv_dsp_dct_execute_device.argtypes = [_vp, _vp, _vp, _sz, _vp]
@@ -408,6 +419,56 @@ class FirPlan:
     def __del__(self):
         if getattr(self, "h", None) and _lib is not None:
             _lib.vv_dsp_fir_plan_destroy(self.h)
+            self.h = None
+
+
+class Resampler:
+    """Fixed-ratio resampler (vv_dsp_resampler_*): out_rate / in_rate = num / den.
+    sinc=False: linear interpolation, bit-identical to the reference; sinc=True:
+    windowed sinc with `taps` taps (clamped to 4..128, raised to even)."""
+
+    def __init__(self, num, den, sinc=False, taps=32):
+        L = lib()
+        self.h = _vp(L.vv_dsp_resampler_create(int(num), int(den)))
+        if not self.h:
+            raise VvError(f"resampler_create({num}, {den}): the ratio's terms must be positive")
+        _check(L.vv_dsp_resampler_set_quality(self.h, 1 if sinc else 0, int(taps)), "resampler_set_quality")
+
+    def set_ratio(self, num, den):
+        _check(lib().vv_dsp_resampler_set_ratio(self.h, int(num), int(den)), "resampler_set_ratio")
+
+    def set_quality(self, sinc, taps=32):
+        _check(lib().vv_dsp_resampler_set_quality(self.h, 1 if sinc else 0, int(taps)), "resampler_set_quality")
+
+    def output_length(self, n):
+        return lib().vv_dsp_resampler_output_length(self.h, int(n))
+
+    def __call__(self, x, out=None, stream=None):
+        """x: (n,) or (nch, n) float32 device tensor (rows with unit sample stride)
+        -> y (output_length(n),) or (nch, output_length(n))."""
+        x2 = x if x.dim() == 2 else x.unsqueeze(0)
+        if x2.dim() != 2 or x2.dtype != torch.float32 or not x2.is_cuda or (x2.shape[1] > 1 and x2.stride(1) != 1):
+            raise VvError("resampler input: float32 device rows with unit sample stride")
+        nch, n = x2.shape
+        m = self.output_length(n)
+        if out is None:
+            out = torch.empty((nch, m), dtype=torch.float32, device=x.device)
+        o2 = out if out.dim() == 2 else out.unsqueeze(0)
+        if o2.dtype != torch.float32 or not o2.is_cuda or o2.shape[0] != nch or o2.shape[1] < m or \
+                (o2.shape[1] > 1 and o2.stride(1) != 1):
+            raise VvError(f"resampler output: float32 device rows, {nch} x at least {m}")
+        got = _sz(0)
+        xs = x2.stride(0) if nch > 1 else n
+        os_ = o2.stride(0) if nch > 1 else o2.shape[1]
+        _check(lib().vv_dsp_resampler_process_device(self.h, C.c_void_p(x2.data_ptr()), n, nch, xs,
+                                                     C.c_void_p(o2.data_ptr()), o2.shape[1], os_, _stream(stream),
+                                                     C.byref(got)), "resampler_process_device")
+        y = o2[:, :got.value]
+        return y if x.dim() == 2 else y[0]
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.vv_dsp_resampler_destroy(self.h)
             self.h = None
 
 
