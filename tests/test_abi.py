@@ -203,6 +203,56 @@ def test_no_gpu_fails_loudly(cpu_lib):
     assert b"no HIP device" in L.vvhip_last_error()
 
 
+def test_last_error_is_one_per_thread_text_for_the_whole_library(amd_lib_path):
+    """vvhip_last_error() reads one per-thread text whichever shim translation
+    unit raised the failure: vvhip_rows_half_device (shim_core.hip, next to
+    vvhip_last_error itself) and vvhip_inst_phase_device (shim_analytic.hip)
+    both land in it, and a thread that has not failed reads an empty text or
+    its own, never another thread's.  No GPU needed: both are argument checks
+    that return before any launch (the pointers are host dummies, never read)."""
+    import threading
+    import numpy as np
+    L = C.CDLL(amd_lib_path)
+    L.vvhip_last_error.restype = C.c_char_p
+    L.vvhip_set_error.argtypes = [C.c_char_p]
+    L.vvhip_rows_half_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]
+    L.vvhip_inst_phase_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
+    buf = np.zeros(64, np.float32)
+    p = buf.ctypes.data
+
+    def overlap():
+        return L.vvhip_rows_half_device(p, p + 8, 2, 8, 0, None)
+
+    def too_many_rows():
+        return L.vvhip_inst_phase_device(p, 4, 65536, p, None)
+
+    L.vvhip_set_error(b"")
+    assert overlap() == ERR_RANGE
+    assert b"overlap" in L.vvhip_last_error()
+    seen = {}
+
+    def other_thread():
+        seen["fresh"] = L.vvhip_last_error()
+        seen["status"] = too_many_rows()
+        seen["own"] = L.vvhip_last_error()
+
+    t = threading.Thread(target=other_thread)
+    t.start()
+    t.join()
+    assert seen["fresh"] == b""
+    assert seen["status"] == ERR_RANGE and b"65535" in seen["own"] and b"overlap" not in seen["own"]
+    err = L.vvhip_last_error()   # this thread's text is still its own
+    assert b"overlap" in err and b"65535" not in err
+    # a failure raised in the other translation unit replaces it
+    assert too_many_rows() == ERR_RANGE
+    err = L.vvhip_last_error()
+    assert b"65535" in err and b"overlap" not in err
+    assert overlap() == ERR_RANGE
+    assert b"overlap" in L.vvhip_last_error()
+    L.vvhip_set_error(b"")
+    assert L.vvhip_last_error() == b""
+
+
 def test_oracle_not_linked_into_product(amd_lib_path):
     """The product must not contain or load the oracle/reference code."""
     import subprocess

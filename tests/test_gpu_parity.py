@@ -873,7 +873,7 @@ def test_dct_nan_policy_matches_reference(amd, ref, policy):
 @pytest.mark.parametrize("chunk_mb", ["1", "3"])
 def test_stft_host_pipeline_matches_device(amd, vdev, orc, chunk_mb, knob):
     """vv_dsp_stft_spectrogram with host buffers above the pipeline threshold runs
-    frame chunks on two lanes (shim.hip run_lanes); chunks start on even frames, so
+    frame chunks on two lanes (shim_common.hpp run_lanes); chunks start on even frames, so
     every frame pair is the one a single launch forms and the rows are
     bit-identical to the one-launch host call; within one f32 ulp of the
     device-pointer call (whose unaligned channel stride sends the zero-padded

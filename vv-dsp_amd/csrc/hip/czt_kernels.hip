@@ -1,6 +1,6 @@
 // czt_kernels.hip -- element-wise stages of the chirp-z transform and of the
 // real cepstrum / minimum-phase family for gfx950.  The transforms between them
-// are the library's own FFT launches (fft_run in shim.hip).
+// are the library's own FFT launches (fft_run in shim_fft.hip).
 //
 // CZT (src/spectral/czt.c:58-178), X[k] = sum_n x[n] A^-n W^(nk), k < M, as
 // Bluestein's convolution with P = next_pow2(N + M - 1):

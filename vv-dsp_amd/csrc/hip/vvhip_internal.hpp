@@ -1,5 +1,5 @@
 // vvhip_internal.hpp -- launchers shared between the kernel translation units
-// and the extern "C" shim (shim.hip).  Not part of the public C ABI.
+// and the extern "C" shim (shim_*.hip).  Not part of the public C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
