@@ -107,7 +107,7 @@ int vvhip_memcpy_d2d_async(void* dst, const void* src, size_t bytes, void* strea
     return 0;
 }
 /* the pack / unpack rule of k_rows_half_pack / k_rows_half_unpack
- * (csrc/hip/stft_kernels.hip): pack keeps bins 0..n/2, unpack mirrors */
+ * (csrc/hip/stft_generic.hip): pack keeps bins 0..n/2, unpack mirrors */
 int vvhip_rows_half_device(const float* in, float* out, size_t rows, size_t n, int unpack, void* stream) {
     (void)stream;
     const size_t h = n / 2 + 1;

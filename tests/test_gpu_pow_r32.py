@@ -1,4 +1,4 @@
-"""k_stft_r32 (stft_kernels.hip): power rows of nfft 1024 / hop 256 with the
+"""k_stft_r32 (stft_r32.hpp, launched from stft_r32.hip): power rows of nfft 1024 / hop 256 with the
 transform split 32 x 32 on half-waves (knob POW_R32 = 1; the default is the
 16 x 16 x 4 ring kernel), against NumPy f64 per
 bin at the power-row tolerance of test_gpu_parity.test_stft_power_rows, against

@@ -1,5 +1,6 @@
 // shim_stft.hip -- STFT handles (device window, per-device copies, host-path
-// staging) over stft_kernels.hip / mixed_fft.hip, and the framing entry points
+// staging) over the STFT units (stft_kernels.hip routes to them; istft_kernels.hip)
+// and mixed_fft.hip, and the framing entry points
 // (framing_kernels.hip).
 #include "shim_common.hpp"
 

@@ -128,7 +128,8 @@ hipError_t launch_take_real(const float2* in, float* out, long long count, hipSt
 hipError_t launch_zero_nyquist_imag(float2* out, long long n, long long batch, long long dist,
                                     hipStream_t s);
 
-// ---- STFT (stft_kernels.hip) -------------------------------------------
+// ---- STFT analysis (stft_kernels.hip routes to stft_pair / stft_small /
+// stft_r32.hip; stft_mel.hip, stft_generic.hip) and synthesis (istft_kernels.hip)
 // mode 0: magnitude rows [frames][nfft]; 1: complex rows [frames][nfft];
 // 2: power rows [frames][nfft/2+1], row_pitch floats apart (0: packed, nfft/2+1)
 bool stft_fused_supported(long long nfft);
