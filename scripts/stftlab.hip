@@ -8,7 +8,10 @@
 #include "../vv-dsp_amd/csrc/hip/debug.hip"
 #include "../vv-dsp_amd/csrc/hip/tables.hip"
 #include "../vv-dsp_amd/csrc/hip/stft_pair.hpp"   // k_stft_pair<1024, 3 | 4, 4> for the occupancy query
-#include "../vv-dsp_amd/csrc/hip/fir_kernels.hip"
+#include "../vv-dsp_amd/csrc/hip/fir_ols.hip"
+#include "../vv-dsp_amd/csrc/hip/fir_1024.hip"
+#include "../vv-dsp_amd/csrc/hip/fir_direct.hip"
+#include "../vv-dsp_amd/csrc/hip/fir_long.hip"
 #include "../vv-dsp_amd/csrc/hip/fft_kernels.hip"
 
 namespace vvh {

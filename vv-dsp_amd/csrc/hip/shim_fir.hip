@@ -1,5 +1,5 @@
-// shim_fir.hip -- FIR handles (device taps + per-block-size spectra H) over
-// fir_kernels.hip: overlap-save, the long-filter four-step path, the direct
+// shim_fir.hip -- FIR handles (device taps + per-block-size spectra H) over the
+// fir_*.hip launchers: overlap-save, the long-filter four-step path, the direct
 // form and filtfilt.
 #include "shim_common.hpp"
 
@@ -96,9 +96,10 @@ static int fir_ols_long(vvhip_fir* f, size_t nr, const float* d_x, float* d_y, s
                         size_t x_stride, size_t y_stride, hipStream_t s) {
     const float2* H = nullptr;
     if (int st = fir_spectrum(f, nr, &H, s)) return st;
-    const long long N = (long long)nr, le = (long long)f->taps - 1, lout = N - le;
-    const long long nblk = ((long long)n + lout - 1) / lout, ppc = (nblk + 1) / 2;
-    const long long items = ppc * (long long)nch;
+    // history taps - 1 as it is (fir_long_block: at most 3/4 of N): the gather needs no aligned block starts
+    const long long N = (long long)nr;
+    const FirGeo g = fir_geometry(N, (long long)f->taps - 1, (long long)n);
+    const long long le = g.le, lout = g.lout, ppc = g.ppc, items = ppc * (long long)nch;
     long long rows = (256LL << 20) / (8 * N);
     if (rows < 1) rows = 1;
     if (rows > items) rows = items;

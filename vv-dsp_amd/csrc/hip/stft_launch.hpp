@@ -34,13 +34,6 @@ inline bool stft_span_ok(const StftJob& j, long long hop_max) {
     return j.hop % 4 == 0 && j.hop <= hop_max && ((uintptr_t)j.sig & 15) == 0 && (j.ch_stride & 3) == 0;
 }
 
-// Blocks of a persistent launch: the kernel's resident grid (computed once per
-// call site, `cache`), at most the `need` blocks the work fills; < 1: nothing to launch.
-inline int capped_grid(int cap, long long need) { return (int)(need < cap ? need : cap); }
-inline int capped_grid(std::atomic<int>& cache, const void* kern, int wg, long long need) {
-    return capped_grid(cached_grid(cache, kern, wg, 0, 1LL << 40), need);
-}
-
 // One k_stft_r32<MODE> launch (kern): `wg` threads walking `cpb` frame-pair
 // couples at a time (4 on 256 threads; the mel modes 8 on 512, one copy of the
 // tables), persistent grid.  With dynamic LDS (the mel plan's tables) the
@@ -79,7 +72,6 @@ struct PairWalk {
     long long grid, chunk;
     unsigned* ctrs;
 };
-inline long long dyn_grid(int cap) { return cap / 8 * 8; }
 inline PairWalk pair_walk(long long pairs, int F, int cap, int capd, bool want_dyn, long long cps_max,
                           hipStream_t s) {
     PairWalk w{false, 0, 0, nullptr};

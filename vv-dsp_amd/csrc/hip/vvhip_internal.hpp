@@ -105,6 +105,14 @@ inline int cached_grid(std::atomic<int>& cache, const void* kernel, int block, s
     }
     return g;
 }
+// Blocks of a persistent launch: the kernel's resident grid (computed once per
+// call site, `cache`), at most the `need` blocks the work fills; < 1: nothing to launch.
+inline int capped_grid(int cap, long long need) { return (int)(need < cap ? need : cap); }
+inline int capped_grid(std::atomic<int>& cache, const void* kern, int wg, long long need) {
+    return capped_grid(cached_grid(cache, kern, wg, 0, 1LL << 40), need);
+}
+// Blocks of a dynamic-walk launch (counters per XCD group): the same number in each of the 8 groups
+inline long long dyn_grid(int cap) { return cap / 8 * 8; }
 
 // ---- pow2 register/LDS FFTs (fft_kernels.hip) -----------------------------
 bool c2c_supported(long long n);           // pow2, 2..4096
@@ -193,8 +201,16 @@ bool istft_fused_supported(long long nfft, long long hop);
 hipError_t launch_istft_fused(long long nfft, long long hop, const float2* spec, long long count,
                               const float* win, float* out_add, float* norm_add, hipStream_t s);
 
-// ---- FIR overlap-save (fir_kernels.hip) ---------------------------------
+// ---- FIR (fir_ols.hip routes to fir_1024.hip; fir_direct.hip, fir_long.hip) ----
 bool fir_ols_supported(long long nfft);
+// Overlap-save geometry of n samples per channel in blocks of nfft with history
+// le (fir_pair.hpp): lout outputs per block, nblk blocks, ppc pairs of blocks;
+// pairs [qf, ql) are the bulk pairs -- input span start 2q*lout - le >= 0 and both
+// blocks' outputs (2q+2)*lout <= n -- or empty (qf = ql = ppc); nfft - le >= 1.
+struct FirGeo {
+    long long le, lout, nblk, ppc, qf, ql;
+};
+FirGeo fir_geometry(long long nfft, long long le, long long n);
 // H: nfft complex bins of FFT(h zero-padded)/nfft.  prefix: [nch][taps-1] chronological or null.
 hipError_t launch_fir_ols(long long nfft, long long taps, const float2* H, const float* x,
                           float* y, long long n, long long nch, long long x_stride,
