@@ -15,6 +15,7 @@
 #include "vv_dsp/spectral/czt.h"
 #include "vv_dsp/envelope/cepstrum.h"
 #include "vv_dsp/envelope/minphase.h"
+#include "vv_dsp/envelope/lpc.h"
 #include "vv_dsp/resample/resampler.h"
 
 #ifdef __cplusplus
@@ -230,6 +231,44 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_icepstrum_minphase_device(const vv_dsp_rea
                                                                 vv_dsp_real* d_x, void* stream);
 VV_DSP_NODISCARD vv_dsp_status vv_dsp_minphase_from_cepstrum_device(const vv_dsp_real* d_c, size_t n, size_t batch,
                                                                     vv_dsp_cpx* d_spec, void* stream);
+/* Linear prediction on `batch` contiguous rows (vv_dsp/envelope/lpc.h, lpc.c:7-72).
+ * _autocorr_: x [batch][n] -> r [batch][order+1].  The sums are not the
+ * reference's sequential ones (64 partial sums and a fixed tree per lag); their
+ * order depends on n alone, never on the batch or the entry point.
+ * _levinson_: r [batch][order+1] -> a [batch][order+1], err [batch], the
+ * reference's recursion, bit-identical to it given the same r.  A row with
+ * r[0] <= 0 (the silent frame, the reference's VV_DSP_ERROR_INTERNAL) gets
+ * a = {1, 0, .., 0} and err = 0; its neighbours are unaffected.
+ * _lpc_: the two in one launch, bit-identical to them in sequence.
+ * Orders <= 32 on rows of n <= 4096 take the wave kernel, any other order < n
+ * a generic one (vvhip_debug_get("STAT_LPC_WAVE") / ("STAT_LPC_GENERIC")). */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_autocorr_device(const vv_dsp_real* d_x, size_t n, size_t order, size_t batch,
+                                                      vv_dsp_real* d_r, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_levinson_device(const vv_dsp_real* d_r, size_t order, size_t batch,
+                                                      vv_dsp_real* d_a, vv_dsp_real* d_err, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpc_device(const vv_dsp_real* d_x, size_t n, size_t order, size_t batch,
+                                                 vv_dsp_real* d_a, vv_dsp_real* d_err, void* stream);
+/* Signal -> framed, windowed LPC in one kernel, no frame rows in HBM: d_signal
+ * [nch][n] (ch_stride floats apart) -> a [nch][frames][order+1] and err
+ * [nch][frames] (channels a_ch_stride / err_ch_stride floats apart), frames =
+ * vv_dsp_get_num_frames(n, frame_len, hop_len, center).  Frame contents are
+ * vv_dsp_fetch_frames_device's (zero padding, reflection when center, times
+ * d_window when not NULL), and the result is bit-identical to that call
+ * followed by vv_dsp_lpc_device.  Zero frames: OK, nothing written.
+ * hop_len = 0, frame_len = 0 or order + 1 > frame_len: INVALID_SIZE. */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpc_frames_device(const vv_dsp_real* d_signal, size_t n, size_t nch,
+                                                        size_t ch_stride, size_t frame_len, size_t hop_len, int center,
+                                                        const vv_dsp_real* d_window, size_t order, vv_dsp_real* d_a,
+                                                        size_t a_ch_stride, vv_dsp_real* d_err, size_t err_ch_stride,
+                                                        void* stream);
+/* a [batch][order+1] -> mag [batch][nfft] = g / |A(e^(j 2 pi k / nfft))|, g =
+ * d_gain[row] (NULL: 1).  levinson_sign 0: A = 1 - sum a[m] z^-m, vv_dsp_lpspec's
+ * (the reference's) convention; nonzero: A = 1 + sum a[m] z^-m, so rows of
+ * vv_dsp_levinson_device / vv_dsp_lpc_device feed it directly.  The phase of
+ * term (m, k) is exact: (m k) mod nfft as an integer. */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpspec_device(const vv_dsp_real* d_a, size_t order, const vv_dsp_real* d_gain,
+                                                    size_t nfft, size_t batch, int levinson_sign, vv_dsp_real* d_mag,
+                                                    void* stream);
 /* Spectral utilities on `batch` contiguous rows of n (utils.c:5-73): fftshift
  * (inverse 0) / ifftshift (inverse 1) of float or complex rows (in place
  * allowed); phase wrap of `count` floats; phase unwrap of each row. */

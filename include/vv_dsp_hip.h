@@ -27,6 +27,7 @@
  *   vvhip_fftshift_* / _phase_wrap_* / _phase_unwrap_*: src/spectral/utils.c:5-73
  *   vvhip_cepstrum_* / _icepstrum_minphase_* / _minphase_from_cepstrum_*:
  *                  src/envelope/cepstrum.c:7-78, src/envelope/minphase.c:7-31
+ *   vvhip_autocorr_* / _levinson_* / _lpc_* / _lpspec_*: src/envelope/lpc.c:7-72
  */
 #ifndef VV_DSP_HIP_H
 #define VV_DSP_HIP_H
@@ -58,8 +59,9 @@ const char* vvhip_last_error(void);
  *       path counter to 0);
  *   vvhip_debug_get(name)  a knob's value (-1 unset) or a path counter
  *       ("STAT_STFT_DYN", "STAT_FIR_DYN", "STAT_FIR_STATIC", "STAT_MEL_FUSED",
- *       "STAT_MEL_SPLIT", "STAT_RESAMPLE_TABLE", "STAT_RESAMPLE_GENERIC": launches
- *       of that path since the last clear); -2 unknown.
+ *       "STAT_MEL_SPLIT", "STAT_RESAMPLE_TABLE", "STAT_RESAMPLE_GENERIC",
+ *       "STAT_LPC_WAVE", "STAT_LPC_GENERIC": launches of that path since the
+ *       last clear); -2 unknown.
  * The environment is read once per process, and only with VVHIP_AB=1 set. */
 int vvhip_debug_set(const char* name, long long value);
 int vvhip_debug_clear(const char* name);
@@ -261,6 +263,37 @@ int vvhip_minphase_from_cepstrum_device(const float* d_c, size_t n, size_t batch
 int vvhip_cepstrum_host(const float* x, size_t n, float* c);
 int vvhip_icepstrum_minphase_host(const float* c, size_t n, float* x);
 int vvhip_minphase_from_cepstrum_host(const float* c, size_t n, float* spec);
+
+/* ---- Linear prediction (src/envelope/lpc.c:7-72) ----
+ * `batch` contiguous rows: x [batch][n] -> r [batch][order+1] (lags 0..order);
+ * r -> a [batch][order+1], err [batch] by the reference's Levinson-Durbin
+ * recursion (A(z) = 1 + sum a[m] z^-m), bit-identical to it given the same r;
+ * lpc = the two in one launch, bit-identical to them in sequence.  A row with
+ * r[0] <= 0 (the reference's INTERNAL) gets a = {1, 0, ..}, err = 0 and sets
+ * *d_flag (an int on the device, may be NULL) to 1.
+ * _lpc_frames_: the same over `frames` frames per channel of signal [nch][n],
+ * gathered as vvhip_fetch_frames_device gathers them, into a [ch][frame][order+1]
+ * and err [ch][frame], channels a_ch_stride / err_ch_stride floats apart.
+ * _lpspec_: mag [batch][nfft] = g / |1 - sum a[m] e^(-j 2 pi m k / nfft)| (the
+ * reference's sign, lpc.c:60-69) or, levinson_sign != 0, g / |1 + sum ..|;
+ * g = d_gain[row], or `gain` when d_gain is NULL.
+ * Orders <= 32 on rows <= 4096 take the wave kernel, any other order < n the
+ * generic kernels; knob LPC_GENERIC = 1 forces those ("STAT_LPC_WAVE" /
+ * "STAT_LPC_GENERIC" count which ran). */
+int vvhip_autocorr_device(const float* d_x, size_t n, size_t order, size_t batch, float* d_r, void* stream);
+int vvhip_levinson_device(const float* d_r, size_t order, size_t batch, float* d_a, float* d_err, int* d_flag,
+                          void* stream);
+int vvhip_lpc_device(const float* d_x, size_t n, size_t order, size_t batch, float* d_a, float* d_err, int* d_flag,
+                     void* stream);
+int vvhip_lpc_frames_device(const float* d_signal, size_t n, size_t nch, size_t ch_stride, size_t frame_len,
+                            size_t hop, size_t frames, int center, const float* d_window, size_t order, float* d_a,
+                            size_t a_ch_stride, float* d_err, size_t err_ch_stride, void* stream);
+int vvhip_lpspec_device(const float* d_a, size_t order, const float* d_gain, float gain, size_t nfft, size_t batch,
+                        int levinson_sign, float* d_mag, void* stream);
+int vvhip_autocorr_host(const float* x, size_t n, size_t order, float* r);
+int vvhip_levinson_host(const float* r, size_t order, float* a, float* err);
+int vvhip_lpc_host(const float* x, size_t n, size_t order, float* a, float* err);
+int vvhip_lpspec_host(const float* a, size_t order, float gain, size_t nfft, float* mag);
 
 /* ---- Spectral utilities (src/spectral/utils.c:5-73) ----
  * `batch` contiguous rows of n: fftshift (inverse 0) / ifftshift (inverse 1) of

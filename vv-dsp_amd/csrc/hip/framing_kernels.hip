@@ -8,35 +8,10 @@
 // rounded multiply), and the overlap-add sums each output sample's
 // contributions in increasing frame order, the order of a caller's loop over
 // frame_index.
+#include "framing_index.hpp"
 #include "vvhip_internal.hpp"
 
 namespace vvh {
-
-// framing.c:21-56 (reflection about the ends, period 2n for far indices)
-__host__ __device__ __forceinline__ long long reflect_index(long long idx, long long n) {
-    if (idx < 0) {
-        long long a = -idx - 1;
-        if (a >= n) {
-            const long long period = 2 * n;
-            a %= period;
-            if (a >= n) a = period - 1 - a;
-        }
-        return a;
-    }
-    if (idx >= n) {
-        long long r = n - 1 - (idx - n);
-        if (r < 0) {
-            r = -r - 1;
-            if (r >= n) {
-                const long long period = 2 * n;
-                r %= period;
-                if (r >= n) r = period - 1 - r;
-            }
-        }
-        return r < 0 ? 0 : (r > n - 1 ? n - 1 : r);
-    }
-    return idx;
-}
 
 // frames [frame0, frame0 + count) -> out[count][len]; one thread per output sample.
 // `sig` holds samples [base, ...) of the n-sample signal (base > 0: a host

@@ -18,11 +18,11 @@ enum Knob : int {
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
-    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_COUNT
+    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_COUNT
 };
 long long knob(Knob k, long long dflt);
 // launches of the paths the tests must see taken (vvhip_debug_get("STAT_..."))
-enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_COUNT };
+enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_COUNT };
 void stat_inc(Stat s);
 
 // Device-resident W_N^k = exp(-2*pi*i*k/N) table, k < N, f32 rounded from double.
@@ -256,6 +256,46 @@ hipError_t launch_resample_table(const float* in, long long in_n, long long nch,
 hipError_t launch_resample_generic(const float* in, long long in_n, long long nch, long long in_stride, float* out,
                                    long long out_n, long long out_stride, double ratio, double cutoff, int taps,
                                    hipStream_t s);
+
+// ---- LPC (lpc_kernels.hip), src/envelope/lpc.c ------------------------------
+// The rows an LPC launch reads: `rows` contiguous rows of len samples
+// (framed 0, frames = rows), or the frames of nch = rows / frames channels
+// gathered as k_fetch_frames gathers them (framed 1: zero padding, reflection
+// when center, times win when not null).
+struct LpcSrc {
+    const float* x = nullptr;
+    long long len = 0, rows = 0, frames = 0;
+    long long sig_n = 0, ch_stride = 0, hop = 0;
+    int framed = 0, center = 0;
+    const float* win = nullptr;
+};
+// Where the coefficient rows go: row (ch, f) = (row / frames, row % frames) at
+// a + ch * a_ch_stride + f * (order + 1) and err + ch * err_ch_stride + f.
+// flag (may be null): set to 1 when a row had r[0] <= 0.
+struct LpcOut {
+    float* a = nullptr;
+    float* err = nullptr;
+    long long frames = 0, a_ch_stride = 0, err_ch_stride = 0;
+    int* flag = nullptr;
+};
+constexpr int LPC_WAVE_ORDER = 32;     // the wave kernel's orders and row lengths
+constexpr int LPC_WAVE_LEN = 4096;
+inline bool lpc_wave_supported(long long len, long long order) {
+    return order <= LPC_WAVE_ORDER && len <= LPC_WAVE_LEN && order < len;
+}
+// wave kernel: autocorrelation rows into r [rows][order + 1] (r not null), or
+// autocorrelation + Levinson into out; lpc_wave_supported shapes only
+hipError_t launch_lpc_wave(const LpcSrc& src, int order, float* r, const LpcOut& out, hipStream_t s);
+// any order < len: one workgroup per row, r [rows][order + 1]
+hipError_t launch_autocorr_generic(const LpcSrc& src, long long order, float* r, hipStream_t s);
+// r [rows][order + 1] -> out, the reference's recursion per row (lpc.c:24-38);
+// generic 0 needs order <= LPC_WAVE_ORDER
+hipError_t launch_levinson(const float* r, long long order, long long rows, int generic, const LpcOut& out,
+                           hipStream_t s);
+// a [batch][order + 1] -> mag [batch][nfft] = g / |1 -+ sum a[m] e^{-j 2 pi m k / nfft}|
+// (plus 0: the reference's 1 - sum, lpc.c:60-69), g = gain[row] or gain1 when gain is null
+hipError_t launch_lpspec(const float* a, long long order, const float* gain, float gain1, long long nfft,
+                         long long batch, int plus, float* mag, hipStream_t s);
 
 // ---- DCT / Hilbert helpers (spectral_kernels.hip) ----------------------
 // single-pass analytic signal / DCT-II (analytic_kernels.hip): rows [batch][n]

@@ -111,6 +111,13 @@ def lib():
     L.vv_dsp_stft_get_sizes.argtypes = [_vp, C.POINTER(_sz), C.POINTER(_sz)]
     for f in ("cepstrum_real", "icepstrum_minphase", "minphase_from_cepstrum"):
         getattr(L, f"vv_dsp_{f}_device").argtypes = [_vp, _sz, _sz, _vp, _vp]
+    L.vv_dsp_autocorr_device.argtypes = [_vp, _sz, _sz, _sz, _vp, _vp]
+    L.vv_dsp_levinson_device.argtypes = [_vp, _sz, _sz, _vp, _vp, _vp]
+    L.vv_dsp_lpc_device.argtypes = [_vp, _sz, _sz, _sz, _vp, _vp, _vp]
+    L.vv_dsp_lpc_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, _sz, _vp, _sz, _vp, _sz, _vp]
+    L.vv_dsp_lpspec_device.argtypes = [_vp, _sz, _vp, _sz, _sz, C.c_int, _vp, _vp]
+    L.vv_dsp_get_num_frames.argtypes = [_sz, _sz, _sz, C.c_int]
+    L.vv_dsp_get_num_frames.restype = _sz
     L.vvhip_fir_block_size.argtypes = [_vp, _sz]
     L.vvhip_fir_block_size.restype = _sz
     L.vv_dsp_amd_set_device.argtypes = [C.c_int]
@@ -605,6 +612,97 @@ def icepstrum_minphase(c, stream=None):
 def minphase_from_cepstrum(c, stream=None):
     """minimum-phase spectrum (complex64, imaginary parts 0) from cepstrum rows (minphase.c:7-31)"""
     return _ceps_rows("vv_dsp_minphase_from_cepstrum_device", c, torch.complex64, "minphase_from_cepstrum", stream)
+
+
+def _rows(x, what, min_len=1):
+    """float32 rows (b, n) of a (n,) or (b, n) device tensor"""
+    if x.dim() not in (1, 2):
+        raise VvError(f"{what}: rows of shape (n,) or (batch, n), got {tuple(x.shape)}")
+    x2 = x if x.dim() == 2 else x.unsqueeze(0)
+    if x2.shape[1] < min_len:
+        raise VvError(f"{what}: rows of {x2.shape[1]} elements, at least {min_len} needed")
+    _expect(x2, torch.float32, x2.shape[0] * x2.shape[1], what)
+    return x2
+
+
+def autocorr(x, order, stream=None):
+    """lags 0..order of float32 rows (lpc.c:7-16): (..., n) -> (..., order + 1)"""
+    x2 = _rows(x, "autocorr input", order + 1)
+    b, n = x2.shape
+    r = torch.empty((b, order + 1), dtype=torch.float32, device=x.device)
+    _check(lib().vv_dsp_autocorr_device(_ptr(x2), n, order, b, _ptr(r), _stream(stream)), "autocorr_device")
+    return r if x.dim() == 2 else r[0]
+
+
+def levinson(r, stream=None):
+    """Levinson-Durbin on autocorrelation rows (lpc.c:18-41): (..., order + 1) ->
+    a (..., order + 1) with A(z) = 1 + sum a[m] z^-m, err (...).  A row with
+    r[0] <= 0 gives a = (1, 0, ..), err = 0."""
+    r2 = _rows(r, "levinson input")
+    b, w = r2.shape
+    a = torch.empty((b, w), dtype=torch.float32, device=r.device)
+    err = torch.empty((b,), dtype=torch.float32, device=r.device)
+    _check(lib().vv_dsp_levinson_device(_ptr(r2), w - 1, b, _ptr(a), _ptr(err), _stream(stream)), "levinson_device")
+    return (a, err) if r.dim() == 2 else (a[0], err[0])
+
+
+def lpc(x, order, stream=None):
+    """autocorr + levinson of float32 rows in one launch, bit-identical to
+    levinson(autocorr(x, order)): (..., n) -> a (..., order + 1), err (...)"""
+    x2 = _rows(x, "lpc input", order + 1)
+    b, n = x2.shape
+    a = torch.empty((b, order + 1), dtype=torch.float32, device=x.device)
+    err = torch.empty((b,), dtype=torch.float32, device=x.device)
+    _check(lib().vv_dsp_lpc_device(_ptr(x2), n, order, b, _ptr(a), _ptr(err), _stream(stream)), "lpc_device")
+    return (a, err) if x.dim() == 2 else (a[0], err[0])
+
+
+def num_frames(n, frame_len, hop, center=False):
+    return lib().vv_dsp_get_num_frames(n, frame_len, hop, int(bool(center)))
+
+
+def lpc_frames(sig, frame_len, hop, order, window=None, center=False, out=None, stream=None):
+    """Signal (nch, n) or (n,) float32 -> a (nch, frames, order + 1), err (nch, frames):
+    the frames of vv_dsp_fetch_frames_device (times `window`, frame_len float32, when
+    given) through lpc() in one kernel, bit-identical to the two steps.  out: (a, err)
+    tensors to write into."""
+    sig2 = sig if sig.dim() == 2 else sig.unsqueeze(0)
+    if sig.dim() not in (1, 2) or sig2.dtype != torch.float32 or sig2.stride(1) != 1 or not sig2.is_cuda:
+        raise VvError("lpc_frames signal: float32 device rows with unit sample stride")
+    if frame_len <= 0 or hop <= 0 or order + 1 > frame_len:
+        raise VvError(f"lpc_frames: frame_len {frame_len}, hop {hop}, order {order}")
+    nch, n = sig2.shape
+    if window is not None:
+        _expect(window, torch.float32, frame_len, "lpc_frames window")
+    fr = num_frames(n, frame_len, hop, center)
+    if out is None:
+        a = torch.empty((nch, fr, order + 1), dtype=torch.float32, device=sig.device)
+        err = torch.empty((nch, fr), dtype=torch.float32, device=sig.device)
+    else:
+        a, err = out
+    _expect(a, torch.float32, nch * fr * (order + 1), "lpc_frames coefficients")
+    _expect(err, torch.float32, nch * fr, "lpc_frames error")
+    # rows may be sig2.stride(0) >= n floats apart (a view of a wider buffer)
+    _check(lib().vv_dsp_lpc_frames_device(_vp(sig2.data_ptr()), n, nch, sig2.stride(0), frame_len, hop,
+                                          int(bool(center)), None if window is None else _ptr(window), order,
+                                          _ptr(a), fr * (order + 1), _ptr(err), fr, _stream(stream)),
+           "lpc_frames_device")
+    return (a, err) if sig.dim() == 2 or out is not None else (a[0], err[0])
+
+
+def lpspec(a, nfft, gain=None, levinson_sign=False, stream=None):
+    """All-pole magnitude rows (lpc.c:55-72): a (..., order + 1) -> (..., nfft),
+    gain / |1 - sum a[m] e^(-j 2 pi m k / nfft)| (the reference's sign) or, with
+    levinson_sign, gain / |1 + sum ..| for rows of levinson() / lpc().  gain: one
+    float32 per row (None: 1)."""
+    a2 = _rows(a, "lpspec coefficients")
+    b, w = a2.shape
+    if gain is not None:
+        _expect(gain, torch.float32, b, "lpspec gain")
+    mag = torch.empty((b, nfft), dtype=torch.float32, device=a.device)
+    _check(lib().vv_dsp_lpspec_device(_ptr(a2), w - 1, None if gain is None else _ptr(gain), nfft, b,
+                                      int(bool(levinson_sign)), _ptr(mag), _stream(stream)), "lpspec_device")
+    return mag if a.dim() == 2 else mag[0]
 
 
 def _ptrs(xs):
