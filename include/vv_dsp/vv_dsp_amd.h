@@ -11,6 +11,8 @@
 #include "vv_dsp/spectral/stft.h"
 #include "vv_dsp/spectral/dct.h"
 #include "vv_dsp/filter/fir.h"
+#include "vv_dsp/filter/iir.h"
+#include "vv_dsp/filter/savgol.h"
 #include "vv_dsp/features/mel.h"
 #include "vv_dsp/spectral/czt.h"
 #include "vv_dsp/envelope/cepstrum.h"
@@ -268,6 +270,42 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpc_frames_device(const vv_dsp_real* d_sig
  * term (m, k) is exact: (m k) mod nfft as an integer. */
 VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpspec_device(const vv_dsp_real* d_a, size_t order, const vv_dsp_real* d_gain,
                                                     size_t nfft, size_t batch, int levinson_sign, vv_dsp_real* d_mag,
+                                                    void* stream);
+/* Biquad cascade on `batch` rows of n samples, x_stride / y_stride floats apart
+ * (vv_dsp/filter/iir.h, iir.c:21-43).  d_coef [num_stages][5] = b0 b1 b2 a1 a2
+ * per stage, one cascade for every row.  d_state [batch][num_stages][2] = z1 z2
+ * per row and stage, read as the incoming state and overwritten with the final
+ * one; NULL: zero state in, none written.  d_y == d_x is allowed.
+ * Rows of n <= 8192 run as one recurrence, bit-identical to the reference,
+ * states included.  Longer rows are cut into chunks of 1024 samples: every
+ * chunk is walked from zero state, the chunk-boundary states are propagated
+ * per row in f64 through the cascade's 1024-step transition matrix, and every
+ * chunk is walked again from its true incoming state (rounded to float).  The
+ * outputs then differ from the reference's by rounding of the same size as its
+ * own error against exact arithmetic.  A row's output depends on that row, the
+ * cascade, its state and n alone.  After a NaN input the reference keeps finite
+ * states in the stages ahead of the poisoned one; on chunked rows every state
+ * is NaN from the next chunk boundary on (the outputs are NaN either way).
+ * Knob IIR_CHUNK: 0 never chunks, k > 0 forces chunks of k samples
+ * (vvhip_debug_get("STAT_IIR_EXACT") / ("STAT_IIR_CHUNKED") count which ran). */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_iir_apply_device(const vv_dsp_real* d_coef, size_t num_stages,
+                                                       vv_dsp_real* d_state, const vv_dsp_real* d_x, vv_dsp_real* d_y,
+                                                       size_t n, size_t batch, size_t x_stride, size_t y_stride,
+                                                       void* stream);
+/* Savitzky-Golay (vv_dsp/filter/savgol.h).  _coeffs: the window h[window_length]
+ * the filter convolves with, host setup in f64 with the reference's operations
+ * (savgol.c:28-162), bit-identical to its coefficients; needs no GPU.
+ * _device: `batch` rows of n samples, x_stride / y_stride floats apart; every
+ * output is the f64 sum in window order, rounded once: bit-identical to the
+ * reference.  d_y == d_x is allowed (the rows are staged).  The thread's NaN
+ * policy applies to the samples as read and to the outputs as written; under
+ * the ERROR policy the call waits for the stream and returns
+ * VV_DSP_ERROR_NAN_INF when either met a NaN or Inf (d_y is then unspecified). */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_savgol_coeffs(int window_length, int polyorder, int deriv, vv_dsp_real delta,
+                                                    vv_dsp_real* h);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_savgol_device(const vv_dsp_real* d_x, size_t n, size_t batch, size_t x_stride,
+                                                    int window_length, int polyorder, int deriv, vv_dsp_real delta,
+                                                    vv_dsp_savgol_mode mode, vv_dsp_real* d_y, size_t y_stride,
                                                     void* stream);
 /* Spectral utilities on `batch` contiguous rows of n (utils.c:5-73): fftshift
  * (inverse 0) / ifftshift (inverse 1) of float or complex rows (in place

@@ -28,6 +28,7 @@
  *   vvhip_cepstrum_* / _icepstrum_minphase_* / _minphase_from_cepstrum_*:
  *                  src/envelope/cepstrum.c:7-78, src/envelope/minphase.c:7-31
  *   vvhip_autocorr_* / _levinson_* / _lpc_* / _lpspec_*: src/envelope/lpc.c:7-72
+ *   vvhip_iir_*  : src/filter/iir.c:21-43;  vvhip_savgol_*: src/filter/savgol.c:164-217
  */
 #ifndef VV_DSP_HIP_H
 #define VV_DSP_HIP_H
@@ -60,8 +61,9 @@ const char* vvhip_last_error(void);
  *   vvhip_debug_get(name)  a knob's value (-1 unset) or a path counter
  *       ("STAT_STFT_DYN", "STAT_FIR_DYN", "STAT_FIR_STATIC", "STAT_MEL_FUSED",
  *       "STAT_MEL_SPLIT", "STAT_RESAMPLE_TABLE", "STAT_RESAMPLE_GENERIC",
- *       "STAT_LPC_WAVE", "STAT_LPC_GENERIC": launches of that path since the
- *       last clear); -2 unknown.
+ *       "STAT_LPC_WAVE", "STAT_LPC_GENERIC", "STAT_IIR_EXACT",
+ *       "STAT_IIR_CHUNKED": launches of that path since the last clear);
+ *       -2 unknown.
  * The environment is read once per process, and only with VVHIP_AB=1 set. */
 int vvhip_debug_set(const char* name, long long value);
 int vvhip_debug_clear(const char* name);
@@ -294,6 +296,28 @@ int vvhip_autocorr_host(const float* x, size_t n, size_t order, float* r);
 int vvhip_levinson_host(const float* r, size_t order, float* a, float* err);
 int vvhip_lpc_host(const float* x, size_t n, size_t order, float* a, float* err);
 int vvhip_lpspec_host(const float* a, size_t order, float gain, size_t nfft, float* mag);
+
+/* ---- Biquad cascade (src/filter/iir.c:21-43) ----
+ * coef [stages][5] = b0 b1 b2 a1 a2, state [rows][stages][2] = z1 z2 (in/out;
+ * NULL: zero in, none written), one cascade for all rows; y may be x.  Rows of
+ * n <= 8192 run as one recurrence (bit-identical to the reference), longer
+ * ones in chunks of 1024 with the boundary states propagated in f64
+ * (iir_kernels.hip).  Knob IIR_CHUNK: 0 never chunks, k > 0 chunks of k;
+ * "STAT_IIR_EXACT" / "STAT_IIR_CHUNKED" count the calls of either route.
+ * _host: one row, coefficients and state in host memory. */
+int vvhip_iir_device(const float* d_coef, size_t stages, float* d_state, const float* d_x, float* d_y, size_t n,
+                     size_t batch, size_t x_stride, size_t y_stride, void* stream);
+int vvhip_iir_host(const float* coef, size_t stages, float* state, const float* x, float* y, size_t n);
+
+/* ---- Savitzky-Golay (src/filter/savgol.c:164-217) ----
+ * h: the window's m coefficients in HOST memory (m odd, <= 257; designed by
+ * vv_dsp_savgol_coeffs, csrc/host/savgol.c) -- they travel as kernel
+ * arguments.  mode as vv_dsp_savgol_mode, nan_policy as core/nan_policy.h
+ * (0..3), applied to the samples read and to the outputs; policy 2 waits for
+ * the stream and returns 5 when either met a NaN or Inf. */
+int vvhip_savgol_device(const float* d_x, size_t n, size_t batch, size_t x_stride, const float* h, int m, int mode,
+                        int nan_policy, float* d_y, size_t y_stride, void* stream);
+int vvhip_savgol_host(const float* x, size_t n, const float* h, int m, int mode, int nan_policy, float* y);
 
 /* ---- Spectral utilities (src/spectral/utils.c:5-73) ----
  * `batch` contiguous rows of n: fftshift (inverse 0) / ifftshift (inverse 1) of

@@ -18,11 +18,11 @@ enum Knob : int {
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
-    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_COUNT
+    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_COUNT
 };
 long long knob(Knob k, long long dflt);
 // launches of the paths the tests must see taken (vvhip_debug_get("STAT_..."))
-enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_COUNT };
+enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_COUNT };
 void stat_inc(Stat s);
 
 // Device-resident W_N^k = exp(-2*pi*i*k/N) table, k < N, f32 rounded from double.
@@ -296,6 +296,42 @@ hipError_t launch_levinson(const float* r, long long order, long long rows, int 
 // (plus 0: the reference's 1 - sum, lpc.c:60-69), g = gain[row] or gain1 when gain is null
 hipError_t launch_lpspec(const float* a, long long order, const float* gain, float gain1, long long nfft,
                          long long batch, int plus, float* mag, hipStream_t s);
+
+// ---- biquad cascade (iir_kernels.hip), src/filter/iir.c:21-43 -----------------
+constexpr int IIR_MAX_STAGES = 8;        // stages one walk holds in registers; longer cascades run in groups
+constexpr int IIR_TILE = 32;             // samples of a sub-row per LDS tile: one 128 B line
+constexpr long long IIR_EXACT_MAX = 8192;   // rows up to here run as one recurrence (N0)
+constexpr long long IIR_CHUNK_LEN = 1024;   // chunk length of longer rows (L)
+// One walk over rows * chunks sub-rows: sub-row (row, c) is samples [c L, min(n, (c + 1) L))
+// of row `row`.  coef [stages][5] = b0 b1 b2 a1 a2 (device).  Sub-row q = row * chunks + c
+// starts from zin[q * zin_stride + 2 s + {0, 1}] (zin null: zero).  write_y 0: no
+// output, final state of every sub-row to zout[q * zout_stride + ..]; write_y 1: y
+// written, and the final state of each row's last chunk to zout[row * zout_stride + ..]
+// (zout null: none).
+struct IirWalk {
+    const float* x = nullptr;
+    float* y = nullptr;
+    long long n = 0, rows = 0, chunks = 1, L = 0, x_stride = 0, y_stride = 0;
+    const float* coef = nullptr;
+    const float* zin = nullptr;
+    float* zout = nullptr;
+    long long zin_stride = 0, zout_stride = 0;
+};
+hipError_t launch_iir_walk(const IirWalk& w, int stages, int write_y, hipStream_t s);
+// phi [2 stages][2 stages] (f64, row-major): the cascade's L-step state transition,
+// from the float coefficients by the homogeneous recurrence on unit states
+hipError_t launch_iir_phi(const float* coef, int stages, long long L, double* phi, hipStream_t s);
+// per row: z_0 = the row's incoming state (zrow [rows][zrow_stride], null: zero),
+// z_{c+1} = phi z_c + zs_c in f64; zin[(row * chunks + c) * 2 stages + i] = (float)z_c
+hipError_t launch_iir_scan(const double* phi, int stages, const float* zs, const float* zrow, long long zrow_stride,
+                           long long rows, long long chunks, float* zin, hipStream_t s);
+
+// ---- Savitzky-Golay (savgol_kernels.hip), src/filter/savgol.c:164-217 ---------
+constexpr int SAVGOL_MAX_WINDOW = 257;
+// h: m coefficients in host memory (passed as kernel arguments); flag (device int,
+// policy 2 only): bit 0 a NaN/Inf sample read, bit 1 a NaN/Inf output
+hipError_t launch_savgol(const float* x, long long n, long long batch, long long x_stride, const float* h, int m,
+                         int mode, int policy, float* y, long long y_stride, int* flag, hipStream_t s);
 
 // ---- DCT / Hilbert helpers (spectral_kernels.hip) ----------------------
 // single-pass analytic signal / DCT-II (analytic_kernels.hip): rows [batch][n]

@@ -116,6 +116,10 @@ def lib():
     L.vv_dsp_lpc_device.argtypes = [_vp, _sz, _sz, _sz, _vp, _vp, _vp]
     L.vv_dsp_lpc_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, _sz, _vp, _sz, _vp, _sz, _vp]
     L.vv_dsp_lpspec_device.argtypes = [_vp, _sz, _vp, _sz, _sz, C.c_int, _vp, _vp]
+    L.vv_dsp_iir_apply_device.argtypes = [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]
+    L.vv_dsp_savgol_coeffs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, _vp]
+    L.vv_dsp_savgol_device.argtypes = [_vp, _sz, _sz, _sz, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp, _sz,
+                                       _vp]
     L.vv_dsp_get_num_frames.argtypes = [_sz, _sz, _sz, C.c_int]
     L.vv_dsp_get_num_frames.restype = _sz
     L.vvhip_fir_block_size.argtypes = [_vp, _sz]
@@ -703,6 +707,69 @@ def lpspec(a, nfft, gain=None, levinson_sign=False, stream=None):
     _check(lib().vv_dsp_lpspec_device(_ptr(a2), w - 1, None if gain is None else _ptr(gain), nfft, b,
                                       int(bool(levinson_sign)), _ptr(mag), _stream(stream)), "lpspec_device")
     return mag if a.dim() == 2 else mag[0]
+
+
+def _strided_rows(x, what):
+    """float32 device rows (b, n) of a (n,) or (b, n) tensor with unit sample
+    stride; the rows may be x.stride(0) floats apart (a view of a wider buffer)"""
+    if x.dim() not in (1, 2):
+        raise VvError(f"{what}: rows of shape (n,) or (batch, n), got {tuple(x.shape)}")
+    x2 = x if x.dim() == 2 else x.unsqueeze(0)
+    if x2.dtype != torch.float32 or not x2.is_cuda or (x2.shape[1] > 1 and x2.stride(1) != 1):
+        raise VvError(f"{what}: float32 device rows with unit sample stride")
+    if x2.shape[0] > 1 and x2.stride(0) < x2.shape[1]:
+        raise VvError(f"{what}: rows {x2.stride(0)} floats apart overlap")
+    return x2
+
+
+def iir(x, sos, state=None, out=None, stream=None):
+    """Biquad cascade over float32 rows (iir.c:21-43): x (..., n) -> y (..., n).
+    sos: (stages, 5) float32 device rows b0 b1 b2 a1 a2, one cascade for all
+    rows.  state: (batch, stages, 2) float32 z1 z2 per row and stage (or
+    (stages, 2) for one row), read as the incoming state and updated in place;
+    None: zero state.  out may be x.  Rows up to 8192 samples are bit-identical
+    to the reference; longer rows are chunked (vv_dsp_iir_apply_device)."""
+    x2 = _strided_rows(x, "iir input")
+    b, n = x2.shape
+    if sos.dim() != 2 or sos.shape[1] != 5:
+        raise VvError(f"iir sos: shape (stages, 5), got {tuple(sos.shape)}")
+    stages = sos.shape[0]
+    _expect(sos, torch.float32, 5 * stages, "iir sos")
+    if state is not None:
+        _expect(state, torch.float32, b * stages * 2, "iir state")
+    y = torch.empty((b, n), dtype=torch.float32, device=x.device) if out is None else out
+    y2 = _strided_rows(y, "iir output")
+    if tuple(y2.shape) != (b, n):
+        raise VvError(f"iir output: shape {tuple(y2.shape)}, expected {(b, n)}")
+    _check(lib().vv_dsp_iir_apply_device(_vp(sos.data_ptr()) if stages else None, stages,
+                                         None if state is None or stages == 0 else _ptr(state), _vp(x2.data_ptr()),
+                                         _vp(y2.data_ptr()), n, b, x2.stride(0) if b > 1 else n,
+                                         y2.stride(0) if b > 1 else n, _stream(stream)), "iir_apply_device")
+    return y if out is not None or x.dim() == 2 else y[0]
+
+
+def savgol_coeffs(window_length, polyorder, deriv=0, delta=1.0):
+    """The Savitzky-Golay window (host setup, bit-identical to the reference's
+    coefficients, no GPU needed): a float32 CPU tensor of window_length values."""
+    h = torch.empty(max(int(window_length), 1), dtype=torch.float32)
+    _check(lib().vv_dsp_savgol_coeffs(window_length, polyorder, deriv, delta, _vp(h.data_ptr())), "savgol_coeffs")
+    return h
+
+
+def savgol(x, window_length, polyorder, deriv=0, delta=1.0, mode=0, out=None, stream=None):
+    """Savitzky-Golay smoothing / differentiation of float32 rows (savgol.c:219-287),
+    bit-identical to the reference: x (..., n) -> (..., n).  mode: 0 reflect,
+    1 constant, 2 nearest, 3 wrap (vv_dsp_savgol_mode).  out may be x."""
+    x2 = _strided_rows(x, "savgol input")
+    b, n = x2.shape
+    y = torch.empty((b, n), dtype=torch.float32, device=x.device) if out is None else out
+    y2 = _strided_rows(y, "savgol output")
+    if tuple(y2.shape) != (b, n):
+        raise VvError(f"savgol output: shape {tuple(y2.shape)}, expected {(b, n)}")
+    _check(lib().vv_dsp_savgol_device(_vp(x2.data_ptr()), n, b, x2.stride(0) if b > 1 else n, window_length, polyorder,
+                                      deriv, delta, int(mode), _vp(y2.data_ptr()), y2.stride(0) if b > 1 else n,
+                                      _stream(stream)), "savgol_device")
+    return y if out is not None or x.dim() == 2 else y[0]
 
 
 def _ptrs(xs):
