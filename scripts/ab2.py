@@ -93,18 +93,20 @@ def _stft(L):
     return h
 
 
-def case_stft_nfft(L, s, nfft, hop, nch=32, seconds=600, sr=48000):
-    """magnitude rows at any nfft (speech lengths: the mixed-radix register kernels)"""
+def case_stft_nfft(L, s, nfft, hop, nch=32, seconds=600, sr=48000, power=False):
+    """magnitude rows (power: rows of bins 0..nfft/2) at any nfft (speech lengths: the
+    mixed-radix register kernels)"""
     n = seconds * sr
     fr = frames_of(n, nfft, hop)
-    sig, out = buf(("stftn", nfft, hop, nch, n), lambda: (torch.rand(nch, n, device="cuda") * 2 - 1,
-                                                          torch.empty(nch, fr, nfft, device="cuda")))
+    w = nfft // 2 + 1 if power else nfft
+    sig, out = buf(("stftn", nfft, hop, nch, n, w), lambda: (torch.rand(nch, n, device="cuda") * 2 - 1,
+                                                             torch.empty(nch, fr, w, device="cuda")))
     h = vp()
     ok(L, L.vv_dsp_stft_create(C.byref(StftParams(nfft, hop, 1)), C.byref(h)), "stft create")
     nf = sz()
-    f = L.vv_dsp_stft_spectrogram_device
-    return (lambda: ok(L, f(h, sig.data_ptr(), n, nch, n, out.data_ptr(), fr * nfft, s, C.byref(nf)), "stft")), \
-        nch * n * 4 + nch * fr * nfft * 4, (lambda: out.clone())
+    f = L.vv_dsp_stft_power_device if power else L.vv_dsp_stft_spectrogram_device
+    return (lambda: ok(L, f(h, sig.data_ptr(), n, nch, n, out.data_ptr(), fr * w, s, C.byref(nf)), "stft")), \
+        nch * n * 4 + nch * fr * w * 4, (lambda: out.clone())
 
 
 def case_stft_cpx(L, s, nfft, hop, nch=8, seconds=120, sr=48000):
@@ -227,13 +229,16 @@ CASES = {
     "mfcc": lambda L, s: case_mel(L, s, True),
     "c2c1024": case_c2c,
     **{f"c2c{n}": (lambda L, s, n=n: case_c2c(L, s, n, (1 << 26) // n)) for n in (16, 32, 64, 128, 256, 512, 2048, 4096, 8192)},
-    **{f"r2c{n}": (lambda L, s, n=n: case_real(L, s, n, (1 << 27) // n, 1)) for n in (16, 32, 64, 128, 256, 400, 480, 960, 1024, 2048, 4096, 8192, 16384)},
+    **{f"r2c{n}": (lambda L, s, n=n: case_real(L, s, n, (1 << 27) // n, 1)) for n in (16, 32, 64, 128, 256, 400, 480, 960, 1000, 1024, 2000, 2048, 4096, 8192, 16384)},
     **{f"c2r{n}": (lambda L, s, n=n: case_real(L, s, n, (1 << 27) // n, 2)) for n in (16, 32, 64, 128, 256, 1024, 2048, 4096, 8192, 16384)},
     **{f"hilbert{n}": (lambda L, s, n=n: case_hilbert(L, s, n, (1 << 26) // n)) for n in (16, 32, 64, 128, 256, 1024, 2048, 4096, 8192)},
     **{f"dct{n}": (lambda L, s, n=n: case_dct(L, s, n, (1 << 27) // n)) for n in (16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192)},
     **{f"c2c{n}": (lambda L, s, n=n: case_c2c(L, s, n, (1 << 26) // n)) for n in (320, 400, 441, 480, 600, 640, 720, 800, 900, 960, 1000, 2000, 3000, 4000)},
-    **{f"stft{n}": (lambda L, s, n=n: case_stft_nfft(L, s, n, n // 4)) for n in (64, 128, 256, 400, 480, 512, 960, 1024, 2048, 4096)},
-    **{f"stftc{n}": (lambda L, s, n=n: case_stft_cpx(L, s, n, n // 4)) for n in (256, 512, 1024, 2048, 4096)},
+    **{f"stft{n}": (lambda L, s, n=n: case_stft_nfft(L, s, n, n // 4)) for n in (64, 128, 256, 400, 480, 512, 600, 960, 1000, 1024, 2048, 4096)},
+    **{f"stftc{n}": (lambda L, s, n=n: case_stft_cpx(L, s, n, n // 4))
+       for n in (256, 400, 512, 900, 960, 1024, 2000, 2048, 4096)},
+    # power rows at the mixed-radix lengths (register kernel; 1000: the plan kernel)
+    **{f"stftp{n}": (lambda L, s, n=n: case_stft_nfft(L, s, n, n // 4, power=True)) for n in (400, 960, 1000)},
 }
 
 

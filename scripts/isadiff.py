@@ -7,7 +7,10 @@ are compiled that way first (in parallel, with the Makefile's flags).  For every
 kernel the instruction stream (comments dropped, local labels renumbered in
 order of appearance) and the kernel descriptor (the `.amdhsa_*` lines: VGPR,
 SGPR, LDS and scratch sizes among them) must be equal, the two sides must define
-the same set of kernels, and no side may define a kernel twice.  Exit status 0
+the same set of kernels, and no side may define a kernel twice.  Kernels are
+matched by their demangled names without `(anonymous namespace)::`, so moving a
+kernel or the type of one of its arguments in or out of an anonymous namespace
+is no difference (names are demangled with binutils' `c++filt`).  Exit status 0
 when all of that holds.
 
     python scripts/isadiff.py --a /path/to/old/csrc/hip/stft_kernels.hip \\
@@ -36,12 +39,13 @@ def assemble(src, tmp, hipcc, arch):
 
 def kernels(path):
     """{kernel: (instruction lines, descriptor lines)} of one assembly file"""
-    lines = open(path).read().split("\n")
+    text = subprocess.run(["c++filt"], input=open(path).read(), capture_output=True, text=True, check=True).stdout
+    lines = text.replace("(anonymous namespace)::", "").split("\n")
     desc, cur = {}, None
     for ln in lines:   # descriptors first: they name the kernels
         t = ln.strip()
         if t.startswith(".amdhsa_kernel "):
-            cur = t.split()[1]
+            cur = t[len(".amdhsa_kernel "):].split(";")[0].strip()
             desc[cur] = []
         elif t == ".end_amdhsa_kernel":
             cur = None
@@ -57,6 +61,8 @@ def kernels(path):
             body[cur] = []
             continue
         if cur is None:
+            continue
+        if t.startswith(".section"):   # not an instruction (and it carries the mangled name)
             continue
         if t.startswith(".Lfunc_end"):
             cur = None

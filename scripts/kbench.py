@@ -454,11 +454,9 @@ CASES = {
     "stftp8192": lambda: case_stft_n(8, 600, 8192, 2048, sr=48000),
     **{f"sqpow{nf}": (lambda nf=nf: case_stft_pow_n(32, 600, nf, nf // 4, sr=48000)) for nf in (400, 480, 960)},
     "sqpow400k16": lambda: case_stft_pow_n(32, 600, 400, 160, sr=16000),
-    # speech lengths at 48 kHz (hop = nfft / 4), and VVHIP_MIX_VAR=1 (the conjugate-symmetric row emit)
+    # speech lengths at 48 kHz (hop = nfft / 4)
     **{f"sq{nf}": (lambda nf=nf: case_stft_n(32, 600, nf, nf // 4, sr=48000))
        for nf in (320, 400, 441, 480, 600, 640, 720, 800, 900, 960)},
-    **{f"sq{nf}v{v}": with_env(lambda nf=nf: case_stft_n(32, 600, nf, nf // 4, sr=48000), "VVHIP_MIX_VAR", str(v))
-       for nf in (320, 400, 441, 480, 600, 640, 720, 800, 900, 960) for v in (1, 3, 4, 5, 6)},
     **{f"r2cmix{n}": (lambda n=n: case_r2c(n, (1 << 27) // n)) for n in (400, 960, 1000)},
     **{f"r2cmix{n}gen": with_env(lambda n=n: case_r2c(n, (1 << 27) // n), "VVHIP_STFT_SQ", "0") for n in (400, 960)},
     **{f"r2cmix{n}full": with_env(lambda n=n: case_r2c(n, (1 << 27) // n), "VVHIP_MIX_R2C_FULL", "1") for n in (400, 1000)},

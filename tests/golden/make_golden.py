@@ -202,7 +202,7 @@ def round2_sets(ref, man):
 
 
 REGISTER_LENGTHS = (320, 400, 441, 480, 600, 640, 720, 800, 900, 960)
-# real rows whose n/2-point transform is a register length (vv-dsp_amd mixed_fft.hip VVH_SQ_HALF_LENGTHS)
+# real rows whose n/2-point transform is a register length (vv-dsp_amd sq_kernel.hpp, the half lengths)
 REGISTER_R2C_LENGTHS = (400, 480) + tuple(2 * n for n in REGISTER_LENGTHS)
 
 

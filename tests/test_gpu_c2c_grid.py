@@ -86,7 +86,7 @@ def test_real_grid_shapes_bit_identical(n, kind):
 @pytest.mark.parametrize("kind", ["c2c", "r2c"])
 def test_mixed_register_grid_bit_identical(n, kind):
     """Speech-length C2C and R2C rows on the two-pass register kernel
-    (mixed_fft.hip k_stft_sq MODE 0 / 5): a non-persistent grid by default, knob
+    (sq_rows.hip k_stft_sq MODE 0 / 5): a non-persistent grid by default, knob
     MIX_TPW = 0 the persistent one -- the same values bit for bit, and the
     default against f64 (fft_kiss.c:76-92 / 120-147 semantics)."""
     batch = 1037

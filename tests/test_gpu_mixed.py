@@ -1,6 +1,7 @@
-"""Mixed-radix FFT (mixed_fft.hip) for 7-smooth lengths that are not powers of
-two, n <= 4096 -- the lengths the reference sends through its O(n^2) DFT
-(src/spectral/fft_kiss.c:76-92, :114-116).
+"""Mixed-radix FFT (mixed_fft.hip and the units it routes to: mixed_plan.hip,
+sq_rows.hip, sq_stft.hip, mixed_fourstep.hip) for 7-smooth lengths that are not
+powers of two, n <= 4096 -- the lengths the reference sends through its O(n^2)
+DFT (src/spectral/fft_kiss.c:76-92, :114-116).
 
 Bars: the reference harness's per-bin tolerance against NumPy f64
 (python/test_fft.py:37-38, rtol = atol = 5e-5), normwise within 4x the error of
@@ -202,6 +203,34 @@ def test_mixed_real_batch_invariant(vdev, amd, n):
         np.testing.assert_array_equal(X[i], amd.fft(x[i], R2C))
 
 
+@pytest.mark.parametrize("n,full", [(45, False), (441, False), (3125, False), (6, True), (400, True), (1000, True)])
+def test_mixed_real_full_rows(vdev, n, full):
+    """Real rows as complex rows with a zero imaginary part (k_fft_mixed MODE 4),
+    a batched device R2C: the route of odd 7-smooth lengths (test_gpu_parity's
+    test_r2c_c2r_vs_numpy sends 3..15 through it from the host API; here one
+    length per thread count), and of even lengths under knob MIX_R2C_FULL=1,
+    where the default is the half-length transform plus the split step.  Per
+    bin against NumPy f64 at the harness tolerance; the even lengths also
+    against the default route's rows, with Im X[n/2] = 0 exactly."""
+    import torch
+    r, a = tolerances()
+    rng = np.random.default_rng(8000 + n)
+    x = (rng.random((5, n)) - 0.5).astype(np.float32)
+    xd = torch.from_numpy(x).cuda()
+    ref = np.fft.rfft(x.astype(np.float64), axis=1)
+    plan = vdev.FftPlan(n, vdev.R2C, vdev.FWD, batch=5)
+    if not full:
+        X = plan(xd).cpu().numpy()
+    else:
+        half = plan(xd).cpu().numpy()
+        with vdev.knobs(MIX_R2C_FULL=1):
+            X = plan(xd).cpu().numpy()
+        assert _nw(X, half) <= 2e-6
+        assert np.all(X[:, -1].imag == 0.0)
+    assert X.shape == ref.shape
+    np.testing.assert_allclose(X, ref, rtol=r, atol=a)
+
+
 def test_round2_golden_gpu(amd, golden):
     """The committed round-2 fixtures through the C ABI: 400-point c2c and
     480-point r2c, and the 400/160 STFT, against NumPy f64 at the harness
@@ -252,7 +281,11 @@ def _per_bin(y, ref, what, r=None, a=None):
 @pytest.mark.parametrize("nfft,hop,nch,n", [(400, 160, 4, 48000), (480, 160, 3, 20011), (960, 320, 2, 30001),
                                            (320, 160, 2, 16000), (441, 220, 2, 44100), (600, 240, 3, 9999),
                                            (640, 320, 1, 32000), (720, 360, 2, 14401), (800, 200, 2, 8000),
-                                           (900, 450, 2, 27000)])
+                                           (900, 450, 2, 27000)] + [
+    # the smallest shapes of the frame-pair rule: one zero-padded frame without a second
+    # (n = nfft - 1), and three frames whose last pair has one frame, running past the end
+    (nfft, nfft // 4, 2, n) for nfft in (320, 400, 441, 480, 600, 640, 720, 800, 900)
+    for n in (nfft - 1, nfft + nfft // 4 + 1)])
 def test_stft_speech_register_kernel(vdev, orc, knob, nfft, hop, nch, n):
     """The two-pass register kernel (k_stft_sq) at every length it serves:
     magnitude, complex and power rows of a multi-channel device STFT against

@@ -1,4 +1,4 @@
-"""Row emit of the register STFT kernel (mixed_fft.hip k_stft_sq, MODE 1): the
+"""Row emit of the register STFT kernel (sq_kernel.hpp k_stft_sq, MODE 1): the
 magnitude rows are staged in LDS and flushed per frame pair as 16 B/lane stores
 (row length a multiple of 4 floats, output 16 B aligned) or 4 B/lane stores
 (441-point rows, or an output view that is not 16 B aligned).  Every flush must

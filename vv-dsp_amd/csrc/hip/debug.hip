@@ -25,7 +25,7 @@ namespace {
 // knob names without the VVHIP_ prefix, in enum Knob order
 constexpr const char* KNOB_NAMES[KNOB_COUNT] = {
     "STFT_CPS",      "STFT_RUN",     "STFT_DBS",     "POW_OLD",     "STFT_RING",   "STFT_DYN",
-    "FS_VAR",        "FS_CHUNK_MB",  "FS_OLD",       "BLUE_UNFUSED", "C2C_MAX",    "STFT_SQ",     "MIX_VAR",
+    "FS_VAR",        "FS_CHUNK_MB",  "FS_OLD",       "BLUE_UNFUSED", "C2C_MAX",    "STFT_SQ",
     "MIX_CHUNK_MB",  "MIX_R2C_FULL", "FIR_OLD",      "FIR_DYN",     "FIR_DIRECT_LDS", "FIR_BLOCK",
     "HOST_CHUNK_MB", "NO_MIXED",     "REAL_PROMOTE", "ISTFT_OLD",   "MEL_FUSED",   "CZT_UNFUSED",
     "CEPS_UNFUSED",  "FIR_R32",      "DIST_SLAB_KB", "POW_R32", "MAG_R32",     "MEL_R32", "C2C_TPW", "C2C_ONE", "REAL_TPW", "ANA_TPW", "MIX_TPW", "C2C_SMALL", "DCT_SMALL", "HIL_SMALL", "REAL_SMALL", "R2C_SMALL", "STFT_STAGE", "STFT_ONE", "MFCC_WIN", "RESAMPLE_GENERIC", "LPC_GENERIC", "IIR_CHUNK",

@@ -14,7 +14,7 @@ namespace vvh {
 // environment read once per process); knob(k, dflt) returns dflt when unset.
 enum Knob : int {
     KNOB_STFT_CPS, KNOB_STFT_RUN, KNOB_STFT_DBS, KNOB_POW_OLD, KNOB_STFT_RING, KNOB_STFT_DYN,
-    KNOB_FS_VAR, KNOB_FS_CHUNK_MB, KNOB_FS_OLD, KNOB_BLUE_UNFUSED, KNOB_C2C_MAX, KNOB_STFT_SQ, KNOB_MIX_VAR,
+    KNOB_FS_VAR, KNOB_FS_CHUNK_MB, KNOB_FS_OLD, KNOB_BLUE_UNFUSED, KNOB_C2C_MAX, KNOB_STFT_SQ,
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
@@ -45,8 +45,8 @@ constexpr long long BLUESTEIN_MIN = 1025;   // below: the f64 O(n^2) DFT (exact-
 bool bluestein_supported(long long n);
 hipError_t launch_bluestein(long long n, int fwd, const void* in, int real_in, float2* out, long long nout,
                             long long batch, long long in_dist, long long out_dist, float scale, hipStream_t s);
-// Mixed-radix Stockham FFT (mixed_fft.hip) for 7-smooth non-power-of-two n
-// <= 4096; same contract as launch_dft_naive, and in == out is allowed.
+// Mixed-radix Stockham FFT (mixed_fft.hip routes to mixed_plan.hip, sq_rows.hip,
+// sq_stft.hip, mixed_fourstep.hip) for 7-smooth non-power-of-two n; same contract as launch_dft_naive, and in == out is allowed.
 bool mixed_supported(long long n);
 bool stft_mixed_supported(long long n);
 hipError_t launch_fft_mixed(long long n, int fwd, const void* in, int real_in, float2* out, long long nout,
