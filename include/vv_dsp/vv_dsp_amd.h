@@ -6,6 +6,7 @@
  * reference's C99 ABI. */
 #ifndef VV_DSP_AMD_H
 #define VV_DSP_AMD_H
+#include <stdint.h>
 #include "vv_dsp/vv_dsp_types.h"
 #include "vv_dsp/spectral/fft.h"
 #include "vv_dsp/spectral/stft.h"
@@ -19,6 +20,7 @@
 #include "vv_dsp/envelope/minphase.h"
 #include "vv_dsp/envelope/lpc.h"
 #include "vv_dsp/resample/resampler.h"
+#include "vv_dsp/core/stats.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -271,6 +273,53 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpc_frames_device(const vv_dsp_real* d_sig
 VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpspec_device(const vv_dsp_real* d_a, size_t order, const vv_dsp_real* d_gain,
                                                     size_t nfft, size_t batch, int levinson_sign, vv_dsp_real* d_mag,
                                                     void* stream);
+/* Array statistics (vv_dsp/core/stats.h, which states the numerics: the exact
+ * class bit-identical to the reference, the f64 class within 1 ulp of it, one
+ * summation order whatever the batch, stride, outputs or entry point).
+ * vv_dsp_stats_out: one pointer per output, NULL = not wanted, else one value
+ * per row; zero_crossings, argmin and argmax are uint32.
+ * _stats_: `batch` rows of n samples, row_stride floats apart.
+ * _stats_frames_: d_signal [nch][n] (ch_stride floats apart) -> planes
+ * [nch][frames] (channels out_ch_stride values apart), frames =
+ * vv_dsp_get_num_frames(n, frame_len, hop_len, center), the frames exactly those
+ * of vv_dsp_fetch_frames_device (zero padding, reflection when center, times
+ * d_window when not NULL); bit-identical to that call followed by
+ * vv_dsp_stats_device, without the frame rows in HBM.
+ * One launch reads each row or frame once from HBM (the second pass of var /
+ * skewness / kurtosis and the frames' overlap come from cache) and writes every
+ * requested output.  No output requested: OK, nothing launched.  A requested
+ * output whose size rule fails (var n < 2, skewness n < 3, kurtosis n < 4, n =
+ * the row or frame length), hop_len == 0 or frame_len == 0: INVALID_SIZE,
+ * nothing written.  Zero frames or rows: OK, nothing written.  n (frame_len)
+ * must be below 2^32.
+ * Rows or frames of up to 16384 samples take the wave kernel (one wave per
+ * row); longer ones the long route (one wave per chunk of 4096 samples, the
+ * chunks' results combined per row in chunk order through scratch).  Knob
+ * STATS_LONG = 1 forces the long route; both give the same bits
+ * (vvhip_debug_get("STAT_STATS_WAVE") / ("STAT_STATS_LONG") count which ran).
+ * A mask without sum, mean, var, skewness and kurtosis runs a kernel with no
+ * f64 sum and no second pass. */
+typedef struct vv_dsp_stats_out {   /* each NULL (not wanted) or one value per row */
+    vv_dsp_real *sum, *mean, *var, *rms, *min, *max, *crest, *skewness, *kurtosis;
+    uint32_t *zero_crossings, *argmin, *argmax;
+} vv_dsp_stats_out;
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_stats_device(const vv_dsp_real* d_x, size_t n, size_t batch, size_t row_stride,
+                                                   const vv_dsp_stats_out* out, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_stats_frames_device(const vv_dsp_real* d_signal, size_t n, size_t nch,
+                                                          size_t ch_stride, size_t frame_len, size_t hop_len,
+                                                          int center, const vv_dsp_real* d_window,
+                                                          const vv_dsp_stats_out* out, size_t out_ch_stride,
+                                                          void* stream);
+/* Lagged correlations of `batch` contiguous rows: x [batch][n] -> r [batch][r_len]
+ * (vv_dsp_autocorrelation), x [batch][nx] and y [batch][ny] -> r [batch][r_len]
+ * (vv_dsp_cross_correlation).  Direct f64 sums, one workgroup per (row, lag),
+ * rounded once; lags with no overlapping sample give 0.  n, nx, ny < 2^32 and
+ * batch * r_len < 2^31. */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_autocorrelation_device(const vv_dsp_real* d_x, size_t n, size_t batch,
+                                                             size_t r_len, int biased, vv_dsp_real* d_r, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_cross_correlation_device(const vv_dsp_real* d_x, size_t nx,
+                                                               const vv_dsp_real* d_y, size_t ny, size_t batch,
+                                                               size_t r_len, vv_dsp_real* d_r, void* stream);
 /* Biquad cascade on `batch` rows of n samples, x_stride / y_stride floats apart
  * (vv_dsp/filter/iir.h, iir.c:21-43).  d_coef [num_stages][5] = b0 b1 b2 a1 a2
  * per stage, one cascade for every row.  d_state [batch][num_stages][2] = z1 z2

@@ -29,11 +29,14 @@
  *                  src/envelope/cepstrum.c:7-78, src/envelope/minphase.c:7-31
  *   vvhip_autocorr_* / _levinson_* / _lpc_* / _lpspec_*: src/envelope/lpc.c:7-72
  *   vvhip_iir_*  : src/filter/iir.c:21-43;  vvhip_savgol_*: src/filter/savgol.c:164-217
+ *   vvhip_stats_* / _autocorrelation_* / _cross_correlation_*: src/core/core.c:42-108,
+ *                  src/core/stats.c:10-139
  */
 #ifndef VV_DSP_HIP_H
 #define VV_DSP_HIP_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -62,7 +65,8 @@ const char* vvhip_last_error(void);
  *       ("STAT_STFT_DYN", "STAT_FIR_DYN", "STAT_FIR_STATIC", "STAT_MEL_FUSED",
  *       "STAT_MEL_SPLIT", "STAT_RESAMPLE_TABLE", "STAT_RESAMPLE_GENERIC",
  *       "STAT_LPC_WAVE", "STAT_LPC_GENERIC", "STAT_IIR_EXACT",
- *       "STAT_IIR_CHUNKED": launches of that path since the last clear);
+ *       "STAT_IIR_CHUNKED", "STAT_STATS_WAVE", "STAT_STATS_LONG": launches of
+ *       that path since the last clear);
  *       -2 unknown.
  * The environment is read once per process, and only with VVHIP_AB=1 set. */
 int vvhip_debug_set(const char* name, long long value);
@@ -318,6 +322,41 @@ int vvhip_iir_host(const float* coef, size_t stages, float* state, const float* 
 int vvhip_savgol_device(const float* d_x, size_t n, size_t batch, size_t x_stride, const float* h, int m, int mode,
                         int nan_policy, float* d_y, size_t y_stride, void* stream);
 int vvhip_savgol_host(const float* x, size_t n, const float* h, int m, int mode, int nan_policy, float* y);
+
+/* ---- Array statistics and lagged correlations (src/core/core.c:42-108,
+ * src/core/stats.c:10-139) ----
+ * vvhip_stats_out: one pointer per output, NULL = not wanted, else one value
+ * per row (the layout of vv_dsp_stats_out, vv_dsp_amd.h).  _stats_: `batch`
+ * rows of n samples row_stride floats apart; _stats_frames_: `frames` frames
+ * per channel of signal [nch][n], gathered as vvhip_fetch_frames_device gathers
+ * them, value of (ch, frame) at out + ch * out_ch_stride + frame.  One launch
+ * writes every requested output; none requested: 0, nothing launched; a
+ * requested output whose size rule fails (var n < 2, skewness n < 3, kurtosis
+ * n < 4): 2, nothing written.  Rows up to 16384 samples take the wave kernel,
+ * longer ones the long route (chunks of 4096 through scratch); knob
+ * STATS_LONG = 1 forces it ("STAT_STATS_WAVE" / "STAT_STATS_LONG" count which
+ * ran); both give the same bits (stats_kernels.hip).
+ * Correlations: x [batch][nx], y [batch][ny] -> r [batch][r_len], r[lag] = the
+ * f64 sum of x[i] y[i + lag] over the overlapping samples, over their count
+ * (biased 0) or over nx (biased 1); 0 where nothing overlaps.
+ * _stats_host: one row; bit k of mask = member k of vvhip_stats_out, float
+ * outputs into vals[k] (k < 9), counts and indices into idx[k - 9]. */
+typedef struct vvhip_stats_out {
+    float *sum, *mean, *var, *rms, *min, *max, *crest, *skewness, *kurtosis;
+    uint32_t *zero_crossings, *argmin, *argmax;
+} vvhip_stats_out;
+int vvhip_stats_device(const float* d_x, size_t n, size_t batch, size_t row_stride, const vvhip_stats_out* out,
+                       void* stream);
+int vvhip_stats_frames_device(const float* d_signal, size_t n, size_t nch, size_t ch_stride, size_t frame_len,
+                              size_t hop, size_t frames, int center, const float* d_window,
+                              const vvhip_stats_out* out, size_t out_ch_stride, void* stream);
+int vvhip_autocorrelation_device(const float* d_x, size_t n, size_t batch, size_t r_len, int biased, float* d_r,
+                                 void* stream);
+int vvhip_cross_correlation_device(const float* d_x, size_t nx, const float* d_y, size_t ny, size_t batch,
+                                   size_t r_len, int biased, float* d_r, void* stream);
+int vvhip_stats_host(const float* x, size_t n, unsigned mask, float* vals, size_t* idx);
+int vvhip_cross_correlation_host(const float* x, size_t nx, const float* y, size_t ny, float* r, size_t r_len,
+                                 int biased);
 
 /* ---- Spectral utilities (src/spectral/utils.c:5-73) ----
  * `batch` contiguous rows of n: fftshift (inverse 0) / ifftshift (inverse 1) of

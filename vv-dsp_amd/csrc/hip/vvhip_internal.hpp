@@ -18,11 +18,11 @@ enum Knob : int {
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
-    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_COUNT
+    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_COUNT
 };
 long long knob(Knob k, long long dflt);
 // launches of the paths the tests must see taken (vvhip_debug_get("STAT_..."))
-enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_COUNT };
+enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_COUNT };
 void stat_inc(Stat s);
 
 // Device-resident W_N^k = exp(-2*pi*i*k/N) table, k < N, f32 rounded from double.
@@ -296,6 +296,56 @@ hipError_t launch_levinson(const float* r, long long order, long long rows, int 
 // (plus 0: the reference's 1 - sum, lpc.c:60-69), g = gain[row] or gain1 when gain is null
 hipError_t launch_lpspec(const float* a, long long order, const float* gain, float gain1, long long nfft,
                          long long batch, int plus, float* mag, hipStream_t s);
+
+// ---- array statistics (stats_kernels.hip), src/core/core.c:42-108, stats.c:10-139 ----
+// The rows a statistics launch reads: `rows` rows of len samples row_stride
+// floats apart (framed 0), or the frames of nch = rows / frames channels
+// gathered as k_fetch_frames gathers them (framed 1).
+struct StatsSrc {
+    const float* x = nullptr;
+    long long len = 0, rows = 0, frames = 0, row_stride = 0;
+    long long sig_n = 0, ch_stride = 0, hop = 0;
+    int framed = 0, center = 0;
+    const float* win = nullptr;
+};
+// the outputs, in the order of vv_dsp_stats_out's members; bit k of a mask = output k
+enum StatsBit : int {
+    STATS_SUM, STATS_MEAN, STATS_VAR, STATS_RMS, STATS_MIN, STATS_MAX, STATS_CREST, STATS_SKEW, STATS_KURT,
+    STATS_ZC, STATS_ARGMIN, STATS_ARGMAX, STATS_NOUT
+};
+constexpr int STATS_NFLOAT = 9;   // outputs [0, 9) are floats, [9, 12) uint32
+// Value of row (ch, f) = (row / src.frames, row % src.frames) at p[k] + ch * ch_stride + f
+// (rows that are not frames: at p[k] + row); p[k] null: output k not wanted.
+struct StatsOut {
+    void* p[STATS_NOUT] = {};
+    long long ch_stride = 0;
+    unsigned mask() const {
+        unsigned m = 0;
+        for (int k = 0; k < STATS_NOUT; ++k)
+            if (p[k]) m |= 1u << k;
+        return m;
+    }
+};
+// outputs that need the f64 sum (and, from var on, the second pass about the mean)
+constexpr unsigned STATS_MOMENT_MASK =
+    1u << STATS_SUM | 1u << STATS_MEAN | 1u << STATS_VAR | 1u << STATS_SKEW | 1u << STATS_KURT;
+constexpr unsigned STATS_CENTRAL_MASK = 1u << STATS_VAR | 1u << STATS_SKEW | 1u << STATS_KURT;
+constexpr long long STATS_CHUNK = 4096;        // samples one wave reduces before its lanes combine
+constexpr long long STATS_WAVE_LEN = 16384;    // rows up to here: one wave walks the row's chunks
+// scratch of the long route: bytes per (row, chunk) and per row
+size_t stats_part_bytes();
+size_t stats_total_bytes();
+// one wave per row (any len < 2^32; the shim sends len <= STATS_WAVE_LEN)
+hipError_t launch_stats_wave(const StatsSrc& src, const StatsOut& out, hipStream_t s);
+// one wave per (row, chunk), then the chunks' partial results combined per row in
+// chunk order: the same sums in the same order as the wave kernel's.
+// parts: rows * chunks * stats_part_bytes(), totals: rows * stats_total_bytes()
+hipError_t launch_stats_long(const StatsSrc& src, const StatsOut& out, void* parts, void* totals, hipStream_t s);
+// r [rows][r_len]: r[lag] = sum_i x[i] y[i + lag] in f64 over the `count` overlapping
+// samples, over count (biased 0) or over nx (biased 1); 0 where count == 0.
+// Rows of x / y are nx / ny floats apart.
+hipError_t launch_xcorr(const float* x, long long nx, const float* y, long long ny, long long rows, long long r_len,
+                        int biased, float* r, hipStream_t s);
 
 // ---- biquad cascade (iir_kernels.hip), src/filter/iir.c:21-43 -----------------
 constexpr int IIR_MAX_STAGES = 8;        // stages one walk holds in registers; longer cascades run in groups

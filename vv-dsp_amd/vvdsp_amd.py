@@ -30,6 +30,17 @@ class StftParams(C.Structure):
     _fields_ = [("fft_size", C.c_size_t), ("hop_size", C.c_size_t), ("window", C.c_int)]
 
 
+class StatsOut(C.Structure):
+    """vv_dsp_stats_out: one device pointer per output, NULL = not wanted"""
+    _fields_ = [(name, C.c_void_p) for name in ("sum", "mean", "var", "rms", "min", "max", "crest", "skewness",
+                                                 "kurtosis", "zero_crossings", "argmin", "argmax")]
+
+
+STATS_NAMES = tuple(name for name, _ in StatsOut._fields_)
+STATS_COUNTS = ("zero_crossings", "argmin", "argmax")          # uint32 on the device, int32 tensors here
+STATS_MIN_LEN = {"var": 2, "skewness": 3, "kurtosis": 4}       # the reference's size rules
+
+
 class VvError(RuntimeError):
     pass
 
@@ -116,6 +127,10 @@ def lib():
     L.vv_dsp_lpc_device.argtypes = [_vp, _sz, _sz, _sz, _vp, _vp, _vp]
     L.vv_dsp_lpc_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, _sz, _vp, _sz, _vp, _sz, _vp]
     L.vv_dsp_lpspec_device.argtypes = [_vp, _sz, _vp, _sz, _sz, C.c_int, _vp, _vp]
+    L.vv_dsp_stats_device.argtypes = [_vp, _sz, _sz, _sz, C.POINTER(StatsOut), _vp]
+    L.vv_dsp_stats_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, C.POINTER(StatsOut), _sz, _vp]
+    L.vv_dsp_autocorrelation_device.argtypes = [_vp, _sz, _sz, _sz, C.c_int, _vp, _vp]
+    L.vv_dsp_cross_correlation_device.argtypes = [_vp, _sz, _vp, _sz, _sz, _sz, _vp, _vp]
     L.vv_dsp_iir_apply_device.argtypes = [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]
     L.vv_dsp_savgol_coeffs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, _vp]
     L.vv_dsp_savgol_device.argtypes = [_vp, _sz, _sz, _sz, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp, _sz,
@@ -707,6 +722,92 @@ def lpspec(a, nfft, gain=None, levinson_sign=False, stream=None):
     _check(lib().vv_dsp_lpspec_device(_ptr(a2), w - 1, None if gain is None else _ptr(gain), nfft, b,
                                       int(bool(levinson_sign)), _ptr(mag), _stream(stream)), "lpspec_device")
     return mag if a.dim() == 2 else mag[0]
+
+
+def _stats_planes(what, length, shape, device, who):
+    """the output tensors of `what` and the vv_dsp_stats_out that points at them"""
+    if isinstance(what, str):
+        what = (what,)
+    planes, out = {}, StatsOut()
+    for name in what:
+        if name not in STATS_NAMES:
+            raise VvError(f"{who}: unknown statistic {name!r} (one of {', '.join(STATS_NAMES)})")
+        if length < STATS_MIN_LEN.get(name, 1):
+            raise VvError(f"{who}: {name} needs rows of at least {STATS_MIN_LEN.get(name, 1)} samples, got {length}")
+        if name not in planes:
+            planes[name] = torch.empty(shape, dtype=torch.int32 if name in STATS_COUNTS else torch.float32,
+                                       device=device)
+            setattr(out, name, planes[name].data_ptr())
+    return planes, out
+
+
+def stats(x, what, stream=None):
+    """Statistics of float32 device rows (vv_dsp/core/stats.h): x (n,) or (batch, n),
+    rows x.stride(0) floats apart -> {name: tensor (batch,) or scalar tensor} for the
+    names in `what` (STATS_NAMES), all from one launch.  zero_crossings, argmin and
+    argmax are int32 views of the uint32 values."""
+    x2 = _strided_rows(x, "stats input")
+    b, n = x2.shape
+    if n < 1:
+        raise VvError("stats input: empty rows")
+    planes, out = _stats_planes(what, n, (b,), x.device, "stats")
+    if planes and b:
+        _check(lib().vv_dsp_stats_device(_vp(x2.data_ptr()), n, b, x2.stride(0) if b > 1 else n, C.byref(out),
+                                         _stream(stream)), "stats_device")
+    return planes if x.dim() == 2 else {k: v[0] for k, v in planes.items()}
+
+
+def stats_frames(sig, frame_len, hop, what, window=None, center=False, stream=None):
+    """Per-frame statistics straight from the signal: sig (nch, n) or (n,) float32 ->
+    {name: (nch, frames) or (frames,)}, the frames of vv_dsp_fetch_frames_device (times
+    `window`, frame_len float32, when given) through stats() in one kernel, bit-identical
+    to the two steps."""
+    sig2 = sig if sig.dim() == 2 else sig.unsqueeze(0)
+    if sig.dim() not in (1, 2) or sig2.dtype != torch.float32 or sig2.stride(1) != 1 or not sig2.is_cuda:
+        raise VvError("stats_frames signal: float32 device rows with unit sample stride")
+    if frame_len <= 0 or hop <= 0:
+        raise VvError(f"stats_frames: frame_len {frame_len}, hop {hop}")
+    nch, n = sig2.shape
+    if window is not None:
+        _expect(window, torch.float32, frame_len, "stats_frames window")
+    fr = num_frames(n, frame_len, hop, center)
+    planes, out = _stats_planes(what, frame_len, (nch, fr), sig.device, "stats_frames")
+    if planes and fr and nch:
+        _check(lib().vv_dsp_stats_frames_device(_vp(sig2.data_ptr()), n, nch, sig2.stride(0), frame_len, hop,
+                                                int(bool(center)), None if window is None else _ptr(window),
+                                                C.byref(out), fr, _stream(stream)), "stats_frames_device")
+    return planes if sig.dim() == 2 else {k: v[0] for k, v in planes.items()}
+
+
+def autocorrelation(x, r_len, biased=False, stream=None):
+    """r[lag] = sum x[i] x[i + lag] in f64 over n (biased) or over the n - lag terms
+    (stats.c:106-122): float32 rows (..., n) -> (..., r_len); lags >= n give 0"""
+    x2 = _rows(x, "autocorrelation input")
+    b, n = x2.shape
+    if r_len <= 0:
+        raise VvError(f"autocorrelation: r_len {r_len}")
+    r = torch.empty((b, r_len), dtype=torch.float32, device=x.device)
+    if b:
+        _check(lib().vv_dsp_autocorrelation_device(_ptr(x2), n, b, r_len, int(bool(biased)), _ptr(r),
+                                                   _stream(stream)), "autocorrelation_device")
+    return r if x.dim() == 2 else r[0]
+
+
+def cross_correlation(x, y, r_len, stream=None):
+    """r[lag] = mean of x[i] y[i + lag] over the overlapping samples (stats.c:124-139):
+    float32 rows x (..., nx), y (..., ny) -> (..., r_len); lags with no overlap give 0"""
+    x2 = _rows(x, "cross_correlation x")
+    y2 = _rows(y, "cross_correlation y")
+    if x.dim() != y.dim() or x2.shape[0] != y2.shape[0]:
+        raise VvError(f"cross_correlation: x {tuple(x.shape)} and y {tuple(y.shape)} differ in rows")
+    if r_len <= 0:
+        raise VvError(f"cross_correlation: r_len {r_len}")
+    b = x2.shape[0]
+    r = torch.empty((b, r_len), dtype=torch.float32, device=x.device)
+    if b:
+        _check(lib().vv_dsp_cross_correlation_device(_ptr(x2), x2.shape[1], _ptr(y2), y2.shape[1], b, r_len, _ptr(r),
+                                                     _stream(stream)), "cross_correlation_device")
+    return r if x.dim() == 2 else r[0]
 
 
 def _strided_rows(x, what):
