@@ -20,6 +20,7 @@
 #include "vv_dsp/envelope/minphase.h"
 #include "vv_dsp/envelope/lpc.h"
 #include "vv_dsp/resample/resampler.h"
+#include "vv_dsp/resample/interpolate.h"
 #include "vv_dsp/core/stats.h"
 
 #ifdef __cplusplus
@@ -164,6 +165,48 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_resampler_process_device(vv_dsp_resampler*
                                                                size_t in_n, size_t nch, size_t in_stride,
                                                                vv_dsp_real* d_out, size_t out_cap, size_t out_stride,
                                                                void* stream, size_t* out_n);
+
+/* Interpolation of rows at arbitrary fractional positions
+ * (vv_dsp/resample/interpolate.h, interpolate.c:4-64): reading a signal along a
+ * curve -- vibrato, pitch and tempo warps, reverse playback, non-rational rates.
+ * _device: `batch` rows of n samples, x_stride floats apart (0: one signal row
+ * read by every output row), at m positions per row from d_pos, rows pos_stride
+ * floats apart (0: one row of positions shared by every signal row), into rows
+ * of m outputs out_stride floats apart.  One launch on `stream`; no alignment of
+ * pointers or strides is required.
+ * _uniform_device: position k is (float)(start + (double)k * step), the f64
+ * product and the f64 sum rounded separately (no fused multiply-add); no
+ * position array is read.
+ * _real_batch: one row, positions and outputs in host memory, staged through the
+ * device once.
+ * Every output is the reference's value for its position, bit for bit:
+ * pos <= 0 gives x[0] and pos >= (float)(n - 1) gives x[n - 1], so -Inf and +Inf
+ * follow the end clamps; the cubic (Catmull-Rom with clamped neighbour indices)
+ * gives x[0] when n < 2, whatever the position; every product and sum is rounded
+ * separately, in the reference's order.  A NaN position, which the reference
+ * leaves undefined, gives a NaN output and touches nothing else.  The thread's
+ * NaN policy is not applied (the reference does not apply it here).
+ * Checks, all before any device work, in this order: a NULL pointer
+ * (NULL_POINTER); n == 0 (INVALID_SIZE, the reference's order); m == 0 or
+ * batch == 0 (OK, nothing written); a non-zero stride shorter than its row, or
+ * out_stride == 0 with batch > 1 (INVALID_SIZE); an unknown method
+ * (OUT_OF_RANGE); n >= 2^31 (INVALID_SIZE, as the resampler).
+ * d_out may not overlap d_x or d_pos; this is not detected.
+ * Where one position row serves several signal rows a workgroup takes its run
+ * of positions through 8 of them; knob INTERP_ROWS = 1 forces one row per
+ * workgroup, and both give the same bits (vvhip_debug_get("STAT_INTERP_ONE") /
+ * ("STAT_INTERP_ROWS") count which ran). */
+typedef enum vv_dsp_interp_method { VV_DSP_INTERP_LINEAR = 0, VV_DSP_INTERP_CUBIC = 1 } vv_dsp_interp_method;
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_interpolate_device(const vv_dsp_real* d_x, size_t n, size_t batch,
+                                                         size_t x_stride, const vv_dsp_real* d_pos, size_t m,
+                                                         size_t pos_stride, vv_dsp_interp_method method,
+                                                         vv_dsp_real* d_out, size_t out_stride, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_interpolate_uniform_device(const vv_dsp_real* d_x, size_t n, size_t batch,
+                                                                 size_t x_stride, double start, double step, size_t m,
+                                                                 vv_dsp_interp_method method, vv_dsp_real* d_out,
+                                                                 size_t out_stride, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_interpolate_real_batch(const vv_dsp_real* x, size_t n, const vv_dsp_real* pos,
+                                                             size_t m, vv_dsp_interp_method method, vv_dsp_real* out);
 
 /* Hilbert analytic signal of `batch` contiguous real[N] rows -> cpx[batch][N] */
 VV_DSP_NODISCARD vv_dsp_status vv_dsp_hilbert_analytic_device(const vv_dsp_real* d_x, size_t N, size_t batch,

@@ -65,7 +65,8 @@ const char* vvhip_last_error(void);
  *       ("STAT_STFT_DYN", "STAT_FIR_DYN", "STAT_FIR_STATIC", "STAT_MEL_FUSED",
  *       "STAT_MEL_SPLIT", "STAT_RESAMPLE_TABLE", "STAT_RESAMPLE_GENERIC",
  *       "STAT_LPC_WAVE", "STAT_LPC_GENERIC", "STAT_IIR_EXACT",
- *       "STAT_IIR_CHUNKED", "STAT_STATS_WAVE", "STAT_STATS_LONG": launches of
+ *       "STAT_IIR_CHUNKED", "STAT_STATS_WAVE", "STAT_STATS_LONG",
+ *       "STAT_INTERP_ONE", "STAT_INTERP_ROWS": launches of
  *       that path since the last clear);
  *       -2 unknown.
  * The environment is read once per process, and only with VVHIP_AB=1 set. */
@@ -235,6 +236,31 @@ int vvhip_resample_linear_device(const float* d_in, size_t in_n, size_t nch, siz
 int vvhip_resample_sinc_device(const float* d_in, size_t in_n, size_t nch, size_t in_stride, float* d_out,
                                size_t out_n, size_t out_stride, double ratio, double cutoff, unsigned taps,
                                const float* d_table, size_t phases, void* stream);
+
+/* ---- Interpolation at arbitrary positions (src/resample/interpolate.c:4-64) ----
+ * `batch` rows of n samples x_stride floats apart (0: one row for every output
+ * row), m positions per row -> rows of m outputs out_stride floats apart, one
+ * launch; no alignment required.  method 0 linear, 1 cubic (Catmull-Rom), each
+ * output the reference's value bit for bit; a NaN position gives that NaN.
+ * _device: d_pos rows pos_stride floats apart, 0: one row of positions shared by
+ * every signal row.  _uniform_device: position k = (float)(start + (double)k *
+ * step), product and sum rounded separately; no position array is read.
+ * Checks, before any device work: null pointers (1); n == 0 (2); m == 0 or
+ * batch == 0 (0, nothing written); a non-zero stride shorter than its row, or
+ * out_stride 0 with batch > 1 (2); an unknown method (3); n >= 2^31 (2).
+ * d_out may not overlap d_x or d_pos (not detected).
+ * vvhip_interp_run_length: consecutive outputs of one row per workgroup.
+ * Where one position array serves several rows a workgroup takes its run through
+ * 8 signal rows, reusing the positions and what they decide; knob INTERP_ROWS = 1
+ * forces one row per workgroup; the bits are the same ("STAT_INTERP_ONE" /
+ * "STAT_INTERP_ROWS" count the launches of either route).
+ * _host: one row, positions and outputs in host memory. */
+size_t vvhip_interp_run_length(void);
+int vvhip_interp_device(const float* d_x, size_t n, size_t batch, size_t x_stride, const float* d_pos, size_t m,
+                        size_t pos_stride, int method, float* d_out, size_t out_stride, void* stream);
+int vvhip_interp_uniform_device(const float* d_x, size_t n, size_t batch, size_t x_stride, double start, double step,
+                                size_t m, int method, float* d_out, size_t out_stride, void* stream);
+int vvhip_interp_host(const float* x, size_t n, const float* pos, size_t m, int method, float* out);
 
 /* ---- Hilbert analytic signal (hilbert.c:14-75) ---- */
 int vvhip_hilbert_host(const float* x, size_t n, float* z_out);

@@ -3,7 +3,7 @@
 //
 //   k_resample_linear : the reference's linear path, bit-identical: the position
 //       (float)((double)k / ratio), the end cases, floorf, and (1 - t) a + t b
-//       with both products and the sum rounded separately.
+//       with both products and the sum rounded separately (interp_rule.hpp).
 //   k_resample_table  : the windowed-sinc path through a polyphase table.  The
 //       ratio is rational, so the fractional position of output k is one of
 //       P = num / gcd values and the reference's per-output sin / cos weights
@@ -20,6 +20,7 @@
 //   k_resample_generic: any ratio; every output evaluates the reference's weights
 //       itself in f64 and normalises by their sum (tables too large for LDS).
 #include "vvhip_internal.hpp"
+#include "interp_rule.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -59,14 +60,7 @@ k_resample_linear(const float* __restrict__ in, long long in_n, long long in_str
             const float t = pos - (float)(unsigned long long)i;
             const float a = x[i];
             const float b = x[i + 1 < in_n ? i + 1 : in_n - 1];
-            // an empty asm on each product keeps hipcc from contracting them into the sum
-            float u = 1.0f - t;
-            asm volatile("" : "+v"(u));
-            float pa = u * a;
-            asm volatile("" : "+v"(pa));
-            float pb = t * b;
-            asm volatile("" : "+v"(pb));
-            y = pa + pb;
+            y = interp_linear_rule(t, a, b);
         }
         yrow[k] = y;
     }

@@ -18,11 +18,11 @@ enum Knob : int {
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
-    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_COUNT
+    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_COUNT
 };
 long long knob(Knob k, long long dflt);
 // launches of the paths the tests must see taken (vvhip_debug_get("STAT_..."))
-enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_COUNT };
+enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_COUNT };
 void stat_inc(Stat s);
 
 // Device-resident W_N^k = exp(-2*pi*i*k/N) table, k < N, f32 rounded from double.
@@ -256,6 +256,29 @@ hipError_t launch_resample_table(const float* in, long long in_n, long long nch,
 hipError_t launch_resample_generic(const float* in, long long in_n, long long nch, long long in_stride, float* out,
                                    long long out_n, long long out_stride, double ratio, double cutoff, int taps,
                                    hipStream_t s);
+
+// ---- interpolation at arbitrary positions (interp_kernels.hip), interpolate.c:4-64 per output ----
+constexpr int INTERP_LINEAR = 0, INTERP_CUBIC = 1;   // vv_dsp_interp_method
+constexpr int INTERP_RUN = 2048;                     // consecutive outputs of one row per workgroup
+// `batch` rows of n samples x_stride floats apart (0: one row read by every output
+// row) at m positions per row -> rows of m outputs out_stride floats apart.
+// Positions: pos not null -- rows of m floats pos_stride apart (0: one row for
+// every signal row); pos null -- position k is (float)(start + (double)k * step),
+// product and sum rounded separately.  n < 2^31.
+struct InterpArgs {
+    const float* x = nullptr;
+    long long n = 0, batch = 0, x_stride = 0;
+    const float* pos = nullptr;
+    long long m = 0, pos_stride = 0;
+    double start = 0.0, step = 0.0;
+    float* out = nullptr;
+    long long out_stride = 0;
+};
+// rows: signal rows one workgroup takes its run of positions through: 1, or
+// INTERP_SHARED_ROWS where one position array serves every row (pos not null,
+// pos_stride == 0), which reuses what each position decides
+constexpr int INTERP_SHARED_ROWS = 8;
+hipError_t launch_interp(const InterpArgs& a, int method, int rows, hipStream_t s);
 
 // ---- LPC (lpc_kernels.hip), src/envelope/lpc.c ------------------------------
 // The rows an LPC launch reads: `rows` contiguous rows of len samples

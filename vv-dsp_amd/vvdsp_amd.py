@@ -94,6 +94,12 @@ def lib():
     L.vv_dsp_resampler_process_device.argtypes = [_vp, _vp, _sz, _sz, _sz, _vp, _sz, _sz, _vp, C.POINTER(_sz)]
     L.vvhip_resample_run_length.argtypes = [C.c_uint, C.c_uint, C.c_uint]
     L.vvhip_resample_run_length.restype = _sz
+    L.vv_dsp_interpolate_device.argtypes = [_vp, _sz, _sz, _sz, _vp, _sz, _sz, C.c_int, _vp, _sz, _vp]
+    L.vv_dsp_interpolate_uniform_device.argtypes = [_vp, _sz, _sz, _sz, C.c_double, C.c_double, _sz, C.c_int, _vp,
+                                                    _sz, _vp]
+    L.vv_dsp_interpolate_real_batch.argtypes = [_vp, _sz, _vp, _sz, C.c_int, _vp]
+    L.vvhip_interp_run_length.argtypes = []
+    L.vvhip_interp_run_length.restype = _sz
     L.vv_dsp_hilbert_analytic_device.argtypes = [_vp, _sz, _sz, _vp, _vp]
     L.vv_dsp_dct_make_plan.argtypes = [_sz, C.c_int, C.c_int, C.POINTER(_vp)]
     L.vv_dsp_dct_execute_device.argtypes = [_vp, _vp, _vp, _sz, _vp]
@@ -871,6 +877,81 @@ def savgol(x, window_length, polyorder, deriv=0, delta=1.0, mode=0, out=None, st
                                       deriv, delta, int(mode), _vp(y2.data_ptr()), y2.stride(0) if b > 1 else n,
                                       _stream(stream)), "savgol_device")
     return y if out is not None or x.dim() == 2 else y[0]
+
+
+INTERP_LINEAR, INTERP_CUBIC = 0, 1
+INTERP_METHODS = {"linear": INTERP_LINEAR, "cubic": INTERP_CUBIC}
+
+
+def _interp_method(method):
+    if method in INTERP_METHODS:
+        return INTERP_METHODS[method]
+    if method in (INTERP_LINEAR, INTERP_CUBIC) and not isinstance(method, bool):
+        return int(method)
+    raise VvError(f"interpolate method: 'linear' or 'cubic', got {method!r}")
+
+
+def _interp_rows(x, m, out, who):
+    """the checked signal rows (b, n) and output rows (b, m) of an interpolation call"""
+    x2 = _strided_rows(x, f"{who} input")
+    b, n = x2.shape
+    if n == 0:
+        raise VvError(f"{who} input: rows of no samples")
+    y = torch.empty((b, m), dtype=torch.float32, device=x.device) if out is None else out
+    y2 = _strided_rows(y, f"{who} output")
+    if tuple(y2.shape) != (b, m):
+        raise VvError(f"{who} output: shape {tuple(y2.shape)}, expected {(b, m)}")
+    if y2.device != x2.device:
+        raise VvError(f"{who} output: on {y2.device}, the input is on {x2.device}")
+    return x2, y, y2
+
+
+def interpolate(x, pos, method="linear", out=None, stream=None):
+    """Rows read at arbitrary fractional positions (interpolate.c:4-64, bit-identical
+    to the reference per output): x (..., n) float32 device rows with unit sample
+    stride, which may be x.stride(0) floats apart -> (..., m).  pos: (m,) float32,
+    one curve shared by every row, or (batch, m), one per row; contiguous, on x's
+    device.  method: "linear" or "cubic" (Catmull-Rom).  Positions at or beyond the
+    ends give the end samples; a NaN position gives NaN.  out may not overlap x or pos."""
+    meth = _interp_method(method)
+    if pos.dim() not in (1, 2) or pos.dtype != torch.float32 or not pos.is_cuda or not pos.is_contiguous():
+        raise VvError("interpolate positions: a contiguous float32 device tensor of shape (m,) or (batch, m)")
+    m = pos.shape[-1]
+    x2, y, y2 = _interp_rows(x, m, out, "interpolate")
+    b, n = x2.shape
+    if pos.device != x2.device:
+        raise VvError(f"interpolate positions: on {pos.device}, the input is on {x2.device}")
+    if pos.dim() == 2 and pos.shape[0] != b:
+        raise VvError(f"interpolate positions: {pos.shape[0]} rows for {b} signal rows")
+    if m and b:
+        _check(lib().vv_dsp_interpolate_device(_vp(x2.data_ptr()), n, b, x2.stride(0) if b > 1 else n,
+                                               _vp(pos.data_ptr()), m, m if pos.dim() == 2 else 0, meth,
+                                               _vp(y2.data_ptr()), y2.stride(0) if b > 1 else m, _stream(stream)),
+               "interpolate_device")
+    return y if out is not None or x.dim() == 2 else y[0]
+
+
+def interpolate_uniform(x, start, step, m, method="linear", out=None, stream=None):
+    """interpolate() at positions (float)(start + k * step), k < m, formed in f64 on
+    the device with the product and the sum rounded separately; no position array
+    is read.  step may be negative (reverse playback) or zero."""
+    meth = _interp_method(method)
+    m = int(m)
+    if m < 0:
+        raise VvError(f"interpolate_uniform: m = {m}")
+    x2, y, y2 = _interp_rows(x, m, out, "interpolate_uniform")
+    b, n = x2.shape
+    if m and b:
+        _check(lib().vv_dsp_interpolate_uniform_device(_vp(x2.data_ptr()), n, b, x2.stride(0) if b > 1 else n,
+                                                       float(start), float(step), m, meth, _vp(y2.data_ptr()),
+                                                       y2.stride(0) if b > 1 else m, _stream(stream)),
+               "interpolate_uniform_device")
+    return y if out is not None or x.dim() == 2 else y[0]
+
+
+def interp_run_length():
+    """consecutive outputs of one row that one workgroup of the interpolation kernel takes"""
+    return lib().vvhip_interp_run_length()
 
 
 def _ptrs(xs):
