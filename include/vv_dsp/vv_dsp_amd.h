@@ -15,6 +15,7 @@
 #include "vv_dsp/filter/iir.h"
 #include "vv_dsp/filter/savgol.h"
 #include "vv_dsp/features/mel.h"
+#include "vv_dsp/features/pitch.h"
 #include "vv_dsp/spectral/czt.h"
 #include "vv_dsp/envelope/cepstrum.h"
 #include "vv_dsp/envelope/minphase.h"
@@ -363,6 +364,40 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_autocorrelation_device(const vv_dsp_real* 
 VV_DSP_NODISCARD vv_dsp_status vv_dsp_cross_correlation_device(const vv_dsp_real* d_x, size_t nx,
                                                                const vv_dsp_real* d_y, size_t ny, size_t batch,
                                                                size_t r_len, vv_dsp_real* d_r, void* stream);
+/* Per-frame pitch by YIN (vv_dsp/features/pitch.h, which states the algorithm,
+ * its numerics and the argument checks, made in its order before any device work).
+ * vv_dsp_pitch_out: one pointer per output, NULL = not wanted, else one value
+ * per row: f0 in Hz (0 = unvoiced), aperiodicity = d' at the chosen lag, lag
+ * (uint32), and cmnd, the curve d'(0 .. tau_max), tau_max + 1 floats per row
+ * (vv_dsp_pitch_lag_range gives tau_max).  No output requested: OK, nothing
+ * launched.  A value depends on the row's samples and the parameters alone.
+ * _pitch_: `batch` rows of n samples, row_stride floats apart; row r's curve
+ * at cmnd + r * cmnd_row_stride (>= tau_max + 1).
+ * _pitch_frames_: d_signal [nch][n] (ch_stride floats apart) -> planes
+ * [nch][frames] (channels out_ch_stride values apart) and curves
+ * [nch][frames][tau_max + 1] (channels cmnd_ch_stride floats apart), frames =
+ * vv_dsp_get_num_frames(n, frame_len, hop_len, center), the frames exactly those
+ * of vv_dsp_fetch_frames_device (zero padding, reflection when center, times
+ * d_window when not NULL); bit-identical to that call followed by
+ * vv_dsp_pitch_device, without the frame rows in HBM.  Zero frames or rows: OK,
+ * nothing written.  hop_len == 0: INVALID_SIZE, as is a stride shorter than
+ * what it steps over.
+ * One kernel, one wave per row, the row in LDS
+ * (vvhip_debug_get("STAT_PITCH_WAVE") counts its launches). */
+typedef struct vv_dsp_pitch_out {   /* each NULL (not wanted) or per row */
+    vv_dsp_real *f0, *aperiodicity;
+    uint32_t* lag;
+    vv_dsp_real* cmnd;
+} vv_dsp_pitch_out;
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_pitch_device(const vv_dsp_real* d_x, size_t n, size_t batch, size_t row_stride,
+                                                   const vv_dsp_pitch_params* params, const vv_dsp_pitch_out* out,
+                                                   size_t cmnd_row_stride, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_pitch_frames_device(const vv_dsp_real* d_signal, size_t n, size_t nch,
+                                                          size_t ch_stride, size_t frame_len, size_t hop_len,
+                                                          int center, const vv_dsp_real* d_window,
+                                                          const vv_dsp_pitch_params* params,
+                                                          const vv_dsp_pitch_out* out, size_t out_ch_stride,
+                                                          size_t cmnd_ch_stride, void* stream);
 /* Biquad cascade on `batch` rows of n samples, x_stride / y_stride floats apart
  * (vv_dsp/filter/iir.h, iir.c:21-43).  d_coef [num_stages][5] = b0 b1 b2 a1 a2
  * per stage, one cascade for every row.  d_state [batch][num_stages][2] = z1 z2

@@ -31,6 +31,7 @@
  *   vvhip_iir_*  : src/filter/iir.c:21-43;  vvhip_savgol_*: src/filter/savgol.c:164-217
  *   vvhip_stats_* / _autocorrelation_* / _cross_correlation_*: src/core/core.c:42-108,
  *                  src/core/stats.c:10-139
+ *   vvhip_pitch_*: no reference source; include/vv_dsp/features/pitch.h defines it
  */
 #ifndef VV_DSP_HIP_H
 #define VV_DSP_HIP_H
@@ -66,7 +67,7 @@ const char* vvhip_last_error(void);
  *       "STAT_MEL_SPLIT", "STAT_RESAMPLE_TABLE", "STAT_RESAMPLE_GENERIC",
  *       "STAT_LPC_WAVE", "STAT_LPC_GENERIC", "STAT_IIR_EXACT",
  *       "STAT_IIR_CHUNKED", "STAT_STATS_WAVE", "STAT_STATS_LONG",
- *       "STAT_INTERP_ONE", "STAT_INTERP_ROWS": launches of
+ *       "STAT_INTERP_ONE", "STAT_INTERP_ROWS", "STAT_PITCH_WAVE": launches of
  *       that path since the last clear);
  *       -2 unknown.
  * The environment is read once per process, and only with VVHIP_AB=1 set. */
@@ -383,6 +384,38 @@ int vvhip_cross_correlation_device(const float* d_x, size_t nx, const float* d_y
 int vvhip_stats_host(const float* x, size_t n, unsigned mask, float* vals, size_t* idx);
 int vvhip_cross_correlation_host(const float* x, size_t nx, const float* y, size_t ny, float* r, size_t r_len,
                                  int biased);
+
+/* ---- Per-frame pitch by YIN (include/vv_dsp/features/pitch.h: the algorithm
+ * and the checks, made in its order before any device work) ----
+ * vvhip_pitch_params / vvhip_pitch_out: the layouts of vv_dsp_pitch_params and
+ * vv_dsp_pitch_out.  _lag_range: host arithmetic, each output may be NULL,
+ * nothing written unless the result is 0.  _pitch_: `batch` rows of n samples
+ * row_stride floats apart, row r's curve at cmnd + r * cmnd_row_stride;
+ * _pitch_frames_: `frames` frames per channel of signal [nch][n], gathered as
+ * vvhip_fetch_frames_device gathers them, value of (ch, frame) at out + ch *
+ * out_ch_stride + frame and its curve at cmnd + ch * cmnd_ch_stride + frame *
+ * (tau_max + 1).  No output wanted: 0, nothing launched.  One kernel, one wave
+ * per row ("STAT_PITCH_WAVE" counts its launches; pitch_kernels.hip).  The row
+ * sits in LDS as f64 where four rows fit 64 KiB and as f32 beyond; knob
+ * PITCH_F32 = 1 forces f32, with the same bits.
+ * _host: one frame in host memory; f0 and aperiodicity may each be NULL. */
+typedef struct vvhip_pitch_params {
+    float sample_rate, fmin, fmax, threshold;
+} vvhip_pitch_params;
+typedef struct vvhip_pitch_out {
+    float *f0, *aperiodicity;
+    uint32_t* lag;
+    float* cmnd;
+} vvhip_pitch_out;
+int vvhip_pitch_lag_range(const vvhip_pitch_params* params, size_t frame_len, size_t* tau_min, size_t* tau_max,
+                          size_t* integration_len);
+int vvhip_pitch_device(const float* d_x, size_t n, size_t batch, size_t row_stride, const vvhip_pitch_params* params,
+                       const vvhip_pitch_out* out, size_t cmnd_row_stride, void* stream);
+int vvhip_pitch_frames_device(const float* d_signal, size_t n, size_t nch, size_t ch_stride, size_t frame_len,
+                              size_t hop, size_t frames, int center, const float* d_window,
+                              const vvhip_pitch_params* params, const vvhip_pitch_out* out, size_t out_ch_stride,
+                              size_t cmnd_ch_stride, void* stream);
+int vvhip_pitch_host(const float* x, size_t n, const vvhip_pitch_params* params, float* f0, float* aperiodicity);
 
 /* ---- Spectral utilities (src/spectral/utils.c:5-73) ----
  * `batch` contiguous rows of n: fftshift (inverse 0) / ifftshift (inverse 1) of

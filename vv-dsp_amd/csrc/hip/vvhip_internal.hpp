@@ -18,11 +18,11 @@ enum Knob : int {
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
-    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_COUNT
+    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_COUNT
 };
 long long knob(Knob k, long long dflt);
 // launches of the paths the tests must see taken (vvhip_debug_get("STAT_..."))
-enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_COUNT };
+enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_PITCH_WAVE, STAT_COUNT };
 void stat_inc(Stat s);
 
 // Device-resident W_N^k = exp(-2*pi*i*k/N) table, k < N, f32 rounded from double.
@@ -369,6 +369,33 @@ hipError_t launch_stats_long(const StatsSrc& src, const StatsOut& out, void* par
 // Rows of x / y are nx / ny floats apart.
 hipError_t launch_xcorr(const float* x, long long nx, const float* y, long long ny, long long rows, long long r_len,
                         int biased, float* r, hipStream_t s);
+
+// ---- per-frame pitch by YIN (pitch_kernels.hip), include/vv_dsp/features/pitch.h ----
+// The rows are described by a StatsSrc (rows, or the frames of a signal).
+constexpr long long PITCH_MAX_FRAME = 16384;     // samples of a row
+constexpr int PITCH_MAX_LAG = 8191;              // tau_max
+constexpr size_t PITCH_LDS_MAX = 128u << 10;     // the longest row as f32 and its lags as f64
+// the lag range of a row of W + tau_max samples (shim_pitch.hip derives and checks
+// it) and the parameters as the kernel compares with them
+struct PitchCfg {
+    double sample_rate = 0.0, threshold = 0.0;
+    int tau_min = 0, tau_max = 0, W = 0;
+};
+// Value of row (ch, f) = (row / src.frames, row % src.frames) at plane + ch * ch_stride + f,
+// its curve d'(0 .. tau_max) at cmnd + ch * cmnd_ch_stride + f * cmnd_row_stride (rows
+// that are not frames: at plane + row and cmnd + row * cmnd_row_stride); null: not wanted.
+struct PitchOut {
+    float* f0 = nullptr;
+    float* aperiodicity = nullptr;
+    unsigned* lag = nullptr;
+    float* cmnd = nullptr;
+    long long ch_stride = 0, cmnd_ch_stride = 0, cmnd_row_stride = 0;
+    bool any() const { return f0 || aperiodicity || lag || cmnd; }
+};
+// one wave per row, one launch; nothing wanted or no rows: nothing launched.
+// The row sits in LDS as f64 where four rows fit 64 KiB, as f32 beyond or with
+// f32_rows (knob PITCH_F32 = 1): the conversion is exact, the bits are the same.
+hipError_t launch_pitch(const StatsSrc& src, const PitchCfg& cfg, const PitchOut& out, bool f32_rows, hipStream_t s);
 
 // ---- biquad cascade (iir_kernels.hip), src/filter/iir.c:21-43 -----------------
 constexpr int IIR_MAX_STAGES = 8;        // stages one walk holds in registers; longer cascades run in groups

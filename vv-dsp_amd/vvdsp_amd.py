@@ -41,6 +41,19 @@ STATS_COUNTS = ("zero_crossings", "argmin", "argmax")          # uint32 on the d
 STATS_MIN_LEN = {"var": 2, "skewness": 3, "kurtosis": 4}       # the reference's size rules
 
 
+class PitchParams(C.Structure):
+    """vv_dsp_pitch_params (vv_dsp/features/pitch.h)"""
+    _fields_ = [("sample_rate", C.c_float), ("fmin", C.c_float), ("fmax", C.c_float), ("threshold", C.c_float)]
+
+
+class PitchOut(C.Structure):
+    """vv_dsp_pitch_out: one device pointer per output, NULL = not wanted"""
+    _fields_ = [(name, C.c_void_p) for name in ("f0", "aperiodicity", "lag", "cmnd")]
+
+
+PITCH_NAMES = tuple(name for name, _ in PitchOut._fields_)
+
+
 class VvError(RuntimeError):
     pass
 
@@ -137,6 +150,11 @@ def lib():
     L.vv_dsp_stats_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, C.POINTER(StatsOut), _sz, _vp]
     L.vv_dsp_autocorrelation_device.argtypes = [_vp, _sz, _sz, _sz, C.c_int, _vp, _vp]
     L.vv_dsp_cross_correlation_device.argtypes = [_vp, _sz, _vp, _sz, _sz, _sz, _vp, _vp]
+    L.vv_dsp_pitch_lag_range.argtypes = [C.POINTER(PitchParams), _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]
+    L.vv_dsp_pitch_yin.argtypes = [_vp, _sz, C.POINTER(PitchParams), _vp, _vp]
+    L.vv_dsp_pitch_device.argtypes = [_vp, _sz, _sz, _sz, C.POINTER(PitchParams), C.POINTER(PitchOut), _sz, _vp]
+    L.vv_dsp_pitch_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, C.POINTER(PitchParams),
+                                             C.POINTER(PitchOut), _sz, _sz, _vp]
     L.vv_dsp_iir_apply_device.argtypes = [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]
     L.vv_dsp_savgol_coeffs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, _vp]
     L.vv_dsp_savgol_device.argtypes = [_vp, _sz, _sz, _sz, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp, _sz,
@@ -782,6 +800,71 @@ def stats_frames(sig, frame_len, hop, what, window=None, center=False, stream=No
         _check(lib().vv_dsp_stats_frames_device(_vp(sig2.data_ptr()), n, nch, sig2.stride(0), frame_len, hop,
                                                 int(bool(center)), None if window is None else _ptr(window),
                                                 C.byref(out), fr, _stream(stream)), "stats_frames_device")
+    return planes if sig.dim() == 2 else {k: v[0] for k, v in planes.items()}
+
+
+def pitch_lag_range(params, frame_len):
+    """(tau_min, tau_max, integration_len) of frames of frame_len samples
+    (vv_dsp_pitch_lag_range; host arithmetic, needs no device)"""
+    if not isinstance(params, PitchParams):
+        raise VvError("pitch: params must be a PitchParams")
+    lo, hi, w = _sz(0), _sz(0), _sz(0)
+    _check(lib().vv_dsp_pitch_lag_range(C.byref(params), frame_len, C.byref(lo), C.byref(hi), C.byref(w)),
+           "pitch_lag_range")
+    return lo.value, hi.value, w.value
+
+
+def _pitch_planes(what, tau_max, shape, device, who):
+    """the output tensors of `what` and the vv_dsp_pitch_out that points at them"""
+    if isinstance(what, str):
+        what = (what,)
+    planes, out = {}, PitchOut()
+    for name in what:
+        if name not in PITCH_NAMES:
+            raise VvError(f"{who}: unknown output {name!r} (one of {', '.join(PITCH_NAMES)})")
+        if name not in planes:
+            planes[name] = torch.empty(shape + (tau_max + 1,) if name == "cmnd" else shape,
+                                       dtype=torch.int32 if name == "lag" else torch.float32, device=device)
+            setattr(out, name, planes[name].data_ptr())
+    return planes, out
+
+
+def pitch(x, params, what, stream=None):
+    """YIN pitch of float32 device rows (vv_dsp/features/pitch.h): x (n,) or (batch, n),
+    rows x.stride(0) floats apart -> {name: tensor} for the names in `what`
+    (PITCH_NAMES): f0, aperiodicity (batch,), lag (batch,) int32, cmnd (batch,
+    tau_max + 1), all from one launch."""
+    x2 = _strided_rows(x, "pitch input")
+    b, n = x2.shape
+    _, tau_max, _ = pitch_lag_range(params, n)
+    planes, out = _pitch_planes(what, tau_max, (b,), x.device, "pitch")
+    if planes and b:
+        _check(lib().vv_dsp_pitch_device(_vp(x2.data_ptr()), n, b, x2.stride(0) if b > 1 else n, C.byref(params),
+                                         C.byref(out), tau_max + 1, _stream(stream)), "pitch_device")
+    return planes if x.dim() == 2 else {k: v[0] for k, v in planes.items()}
+
+
+def pitch_frames(sig, frame_len, hop, params, what, window=None, center=False, stream=None):
+    """Per-frame YIN pitch straight from the signal: sig (nch, n) or (n,) float32 ->
+    {name: (nch, frames[, tau_max + 1]) or (frames[, tau_max + 1])}, the frames of
+    vv_dsp_fetch_frames_device (times `window`, frame_len float32, when given) through
+    pitch() in one kernel, bit-identical to the two steps."""
+    sig2 = sig if sig.dim() == 2 else sig.unsqueeze(0)
+    if sig.dim() not in (1, 2) or sig2.dtype != torch.float32 or sig2.stride(1) != 1 or not sig2.is_cuda:
+        raise VvError("pitch_frames signal: float32 device rows with unit sample stride")
+    if frame_len <= 0 or hop <= 0:
+        raise VvError(f"pitch_frames: frame_len {frame_len}, hop {hop}")
+    nch, n = sig2.shape
+    if window is not None:
+        _expect(window, torch.float32, frame_len, "pitch_frames window")
+    _, tau_max, _ = pitch_lag_range(params, frame_len)
+    fr = num_frames(n, frame_len, hop, center)
+    planes, out = _pitch_planes(what, tau_max, (nch, fr), sig.device, "pitch_frames")
+    if planes and fr and nch:
+        _check(lib().vv_dsp_pitch_frames_device(_vp(sig2.data_ptr()), n, nch, sig2.stride(0), frame_len, hop,
+                                                int(bool(center)), None if window is None else _ptr(window),
+                                                C.byref(params), C.byref(out), fr, fr * (tau_max + 1),
+                                                _stream(stream)), "pitch_frames_device")
     return planes if sig.dim() == 2 else {k: v[0] for k, v in planes.items()}
 
 
