@@ -250,7 +250,9 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_log_mel_pitched_device(const vv_dsp_mfcc_p
  * nfft = 1024, hop <= 256 and a multiple of 4, the signal 16-B aligned with
  * ch_stride a multiple of 4, n_mels <= 128 (log-mel) or n_mels <= 60 and
  * num_mfcc_coeffs <= 64 (MFCC: the log-mel rows stay in the exchange buffer's
- * spare tail); any other shape runs the two steps through a scratch buffer
+ * spare tail), and a filterbank whose chunk schedule has at most 256 chunks
+ * (four per lane; 128 bands over 0-24 kHz at 48 kHz have 308); any other
+ * shape runs the two steps through a scratch buffer
  * (vvhip_debug_get("STAT_MEL_FUSED") / ("STAT_MEL_SPLIT") count which ran).
  * The plan's n_fft must equal the stft's nfft (VV_DSP_ERROR_INVALID_SIZE). */
 VV_DSP_NODISCARD vv_dsp_status vv_dsp_stft_log_mel_device(vv_dsp_stft* h, const vv_dsp_mfcc_plan* plan,

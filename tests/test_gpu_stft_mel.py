@@ -64,6 +64,45 @@ def test_stft_mel_equals_two_step(vdev, nfft, hop, sr, n_mels, n_coeffs, nch, n,
         assert torch.allclose(got16, ref, rtol=1e-4, atol=1e-4)
 
 
+# The plan grid of tests/mel_util.py at nfft 1024 (tests/test_gpu_mel_plans.py
+# pins the two device steps of each to float64), with the path each must take
+# (launch_stft_mel): one kernel for M <= 128 and at most 256 chunks, and for
+# MFCC also M <= 60 and C <= 64; the two launches otherwise.
+FUSED, SPLIT = (1, 0), (0, 1)
+PLAN_PATHS = {   # plan: (log-mel, MFCC)
+    "P1": (FUSED, FUSED), "P2": (FUSED, FUSED), "P3": (FUSED, FUSED), "P4": (FUSED, FUSED), "P5": (FUSED, FUSED),
+    "P6": (FUSED, SPLIT), "P7": (FUSED, SPLIT),   # M > 60: the log-mel rows do not fit the exchange buffer's tail
+    "P8": (SPLIT, SPLIT),                         # 308 chunks
+    "P9": (SPLIT, SPLIT),                         # M > 128
+    "P10": (FUSED, FUSED), "P11": (FUSED, FUSED),
+}
+
+
+@pytest.mark.parametrize("log_mel", [True, False])
+# n: 7 frames at hop 256 and 13 at hop 128 (odd: the pair whose second frame does not exist); shorter than one frame
+@pytest.mark.parametrize("n", [1024 + 5 * 256 + 128, 700])
+@pytest.mark.parametrize("hop", [256, 128])
+@pytest.mark.parametrize("name", list(PLAN_PATHS))
+def test_stft_mel_plan_grid(vdev, name, hop, n, log_mel):
+    import torch
+    from mel_util import PLANS
+    nfft, n_mels, sr, fmin, fmax, n_coeffs, lifter, _ = PLANS[name]
+    nch = 2
+    g = torch.Generator(device="cuda").manual_seed(n_mels + hop + n)
+    sig = torch.rand(nch, n, device="cuda", generator=g) * 2 - 1
+    st = vdev.Stft(nfft, hop)
+    assert n % 4 == 0 and st.frames(n) % 2 == 1
+    mf = vdev.Mfcc(nfft, n_mels, n_coeffs, sr, fmin, fmax, lifter=lifter)
+    ref = _two_step(vdev, st, mf, sig, log_mel)
+    f0, s0 = vv.debug_get("STAT_MEL_FUSED"), vv.debug_get("STAT_MEL_SPLIT")
+    got = mf.from_signal(st, sig, log_mel=log_mel)
+    torch.cuda.synchronize()
+    assert (vv.debug_get("STAT_MEL_FUSED") - f0, vv.debug_get("STAT_MEL_SPLIT") - s0) == \
+        PLAN_PATHS[name][0 if log_mel else 1]
+    assert got.shape == ref.shape == (nch, st.frames(n), n_mels if log_mel else n_coeffs)
+    assert torch.equal(got, ref)
+
+
 @pytest.mark.parametrize("log_mel", [True, False])
 def test_stft_mel_r32_path_taken(vdev, log_mel):
     """knobs POW_R32 = MEL_R32 = 1, hop 256, 8 B aligned channels: the fused rows

@@ -179,7 +179,8 @@ struct MelArgs {
 // signal: the power rows of launch_stft mode 2 feed k_mel_grp's arithmetic in
 // the same kernel, never written to HBM (bit-identical to the two launches).
 // hipErrorNotSupported when the fused kernel does not take this shape
-// (nfft != 1024, hop / alignment, M > 128, C > 64): the caller runs the two launches.
+// (nfft != 1024, hop / alignment, M > 128, more than 64 * MEL_MAX_ROUNDS chunks;
+// MFCC also M > 60 or C > 64): the caller runs the two launches.
 hipError_t launch_stft_mel(int kind, long long nfft, long long hop, const float* sig, long long n, long long nch,
                            long long ch_stride, long long frames, const float* win, const MelArgs& mel, float* out,
                            long long out_ch_stride, hipStream_t s);
