@@ -12,7 +12,9 @@
 #include "../vv-dsp_amd/csrc/hip/fir_1024.hip"
 #include "../vv-dsp_amd/csrc/hip/fir_direct.hip"
 #include "../vv-dsp_amd/csrc/hip/fir_long.hip"
-#include "../vv-dsp_amd/csrc/hip/fft_kernels.hip"
+#include "../vv-dsp_amd/csrc/hip/fft_c2c.hip"
+#include "../vv-dsp_amd/csrc/hip/fft_real.hip"
+#include "../vv-dsp_amd/csrc/hip/fft_glue.hip"
 
 namespace vvh {
 // ------------------------------------------------------------------------

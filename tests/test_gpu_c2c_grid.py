@@ -1,4 +1,4 @@
-"""Batched C2C launch shapes (fft_kernels.hip run_c2c): for 256..4096 points the
+"""Batched C2C launch shapes (fft_c2c.hip run_c2c): for 256..4096 points the
 default is a non-persistent grid, one transform per wave slot, on the loop-free
 kernel (k_c2c<N, FWD, true>); knob C2C_ONE = 0 runs the looping kernel on the
 same grid, C2C_TPW = 0 the persistent grid with its one-transform prefetch, and
@@ -22,13 +22,14 @@ def _x(n, batch, seed):
                          torch.rand(batch, n, device="cuda", generator=g) - 0.5)
 
 
-@pytest.mark.parametrize("n", [16, 32, 64, 128, 256, 1024, 2048, 4096])
+@pytest.mark.parametrize("n", [2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192])
 @pytest.mark.parametrize("fwd", [True, False])
 def test_c2c_grid_shapes_bit_identical(n, fwd):
     """(16..128 points: the default stages each wave's 1024-point block through
     LDS; knob C2C_SMALL = 0 the persistent strided kernel.)  Batch 1031: the last
-    wave's block is partial."""
-    batch = 1031
+    wave's block is partial.  8192 points (one transform per 512-thread workgroup):
+    batch 37."""
+    batch = 37 if n == 8192 else 1031
     x = _x(n, batch, n + fwd)
     p = vv.FftPlan(n, vv.C2C, vv.FWD if fwd else vv.BWD, batch=batch)
     ref = p(x).clone()
@@ -54,13 +55,14 @@ def test_c2c_one_transform_in_place():
     assert torch.equal(y.view(torch.int64), ref.view(torch.int64))
 
 
-@pytest.mark.parametrize("n", [32, 64, 128, 256, 1024, 4096])
+@pytest.mark.parametrize("n", [4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384])
 @pytest.mark.parametrize("kind", ["r2c", "c2r"])
 def test_real_grid_shapes_bit_identical(n, kind):
     """R2C / C2R (fft_kiss.c:120-174 semantics): C2R of n <= 1024 launches one
     transform per slot on a non-persistent grid by default; knob REAL_TPW = 0 / 1
-    forces the persistent / one-per-slot grid -- the same values bit for bit."""
-    batch, h = 1029, n // 2 + 1
+    forces the persistent / one-per-slot grid -- the same values bit for bit.
+    (8192 / 16384 points, one transform per workgroup: batch 37.)"""
+    batch, h = 37 if n >= 8192 else 1029, n // 2 + 1
     g = torch.Generator(device="cuda").manual_seed(n)
     if kind == "r2c":
         x = torch.rand(batch, n, device="cuda", generator=g) - 0.5
@@ -177,3 +179,83 @@ def test_small_real_rows_unaligned_buffers(n, kind):
         if a.dtype == torch.complex64:
             a, b = a.view(torch.float32), b.view(torch.float32)
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+_STAGED = [("c2c", 16), ("c2c", 128), ("r2c", 32), ("r2c", 128), ("c2r", 32), ("c2r", 128),
+           ("hilbert", 16), ("hilbert", 128), ("dct", 16), ("dct", 128)]
+_GUARD = 3   # NaN rows behind the output
+
+
+@pytest.mark.parametrize("batch", [1, 3, 65, 257])
+@pytest.mark.parametrize("kind,n", _STAGED)
+def test_small_staged_partial_blocks(kind, n, batch):
+    """The staged 16..128-point kernels on batches below and just past one wave
+    block: 1 (less than one lane row of a block), 3 (odd: the Hilbert / DCT-II
+    pair without a second row), 65 (one block and a sliver: the other waves
+    leave at nval == 0) and 257 (one workgroup plus one row).  The staged
+    default equals the strided kernel (knob C2C_SMALL / R2C_SMALL / REAL_SMALL /
+    HIL_SMALL = 0) bit for bit -- DCT-II, whose staged kernel contracts
+    differently, within 1e-6 of DCT_SMALL = 0 --, meets its sibling test's f64
+    bound, and writes nothing into the NaN rows behind the batch."""
+    h = n // 2 + 1
+    g = torch.Generator(device="cuda").manual_seed(1000 * n + batch)
+    L = vv.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    rnd = lambda *shape: torch.rand(*shape, device="cuda", generator=g) - 0.5   # noqa: E731
+    if kind == "c2c":
+        x, odt, ow, knob = torch.complex(rnd(batch, n), rnd(batch, n)), torch.complex64, n, "C2C_SMALL"
+        p = vv.FftPlan(n, vv.C2C, vv.FWD, batch=batch)
+    elif kind == "r2c":
+        x, odt, ow, knob = rnd(batch, n), torch.complex64, h, "R2C_SMALL"
+        p = vv.FftPlan(n, vv.R2C, vv.FWD, batch=batch)
+    elif kind == "c2r":
+        x, odt, ow, knob = torch.complex(rnd(batch, h), rnd(batch, h)), torch.float32, n, "REAL_SMALL"
+        p = vv.FftPlan(n, vv.C2R, vv.BWD, batch=batch)
+    elif kind == "hilbert":
+        x, odt, ow, knob = rnd(batch, n), torch.complex64, n, "HIL_SMALL"
+    else:
+        x, odt, ow, knob = rnd(batch, n), torch.float32, n, "DCT_SMALL"
+
+    def run():
+        """the rows and the guard rows behind them, as float32 bits"""
+        per = 2 if odt == torch.complex64 else 1
+        full = torch.full((batch + _GUARD, ow * per), float("nan"), device="cuda")   # every float a NaN
+        y = torch.view_as_complex(full[:batch].view(batch, ow, 2)) if per == 2 else full[:batch]
+        assert x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0   # the staged kernels' gate
+        if kind in ("c2c", "r2c", "c2r"):
+            p(x, out=y)
+        elif kind == "hilbert":
+            assert L.vv_dsp_hilbert_analytic_device(C.c_void_p(x.data_ptr()), n, batch, C.c_void_p(y.data_ptr()),
+                                                    C.c_void_p(s)) == 0
+        else:
+            pl = C.c_void_p()
+            assert L.vv_dsp_dct_make_plan(n, 2, 1, C.byref(pl)) == 0
+            assert L.vv_dsp_dct_execute_device(pl, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), batch,
+                                               C.c_void_p(s)) == 0
+            L.vv_dsp_dct_destroy(pl)
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(full[batch:]).all()), "rows behind the batch were written"
+        return y.clone()
+
+    got = run()
+    with vv.knobs(**{knob: 0}):
+        ref = run()
+    xn = x.cpu().numpy().astype(np.complex128 if x.is_complex() else np.float64)
+    gn = got.cpu().numpy()
+    if kind == "dct":
+        import scipy.fft
+        want = scipy.fft.dct(xn, type=2, axis=1) / 2
+        assert np.abs(gn - want).max() <= 5e-5 + 5e-5 * np.abs(want).max()
+        assert np.allclose(gn, ref.cpu().numpy(), rtol=1e-6, atol=1e-6)
+        return
+    a, b = (torch.view_as_real(t) if t.is_complex() else t for t in (got, ref))
+    assert torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+    if kind == "hilbert":
+        import scipy.signal
+        want = scipy.signal.hilbert(xn, axis=1)
+        bound = 2e-6 * max(1.0, np.log2(n))   # test_hilbert_batched_device's
+    else:
+        want = {"c2c": np.fft.fft, "r2c": np.fft.rfft}[kind](xn, axis=1) if kind != "c2r" else np.fft.irfft(xn, n=n, axis=1)
+        bound = 1e-5                          # the grid tests' above
+    err = np.abs(gn - want).max() / np.abs(want).max()
+    assert err <= bound, err

@@ -17,7 +17,7 @@
 // Minimum phase (cepstrum.c:43-78, minphase.c:7-31): the causal fold of a
 // cepstrum (c0, 2c1 .. 2c(n/2-1), 0 ..), a C2C FFT, then exp of the real part.
 #include "fft_core.hpp"
-#include "vvhip_internal.hpp"
+#include "pow2_launch.hpp"
 
 namespace vvh {
 
@@ -197,16 +197,14 @@ k_czt_fused(const void* __restrict__ x, long long n, long long m, long long rows
 template <int P>
 static hipError_t run_czt_fused(const void* x, int real_in, long long n, long long m, long long rows,
                                 const float2* g, const float2* Bs, const float2* post, float2* X, hipStream_t s) {
-    const float2* tab = twiddle_table(P);
-    const float2* pas = pass_twiddles(P);
-    if (!tab || !pas) return hipErrorOutOfMemory;
+    const Pow2Tables tb(P);
+    if (!tb.ok()) return hipErrorOutOfMemory;
     constexpr int WG = Wg<P>::value, F = Wg<P>::F;
     static std::atomic<int> capc[2];
     auto go = [&](auto kern, int ri) {
         const int cap = cached_grid(capc[ri], (const void*)kern, WG, 0, 1LL << 40);
-        const long long need = (rows + F - 1) / F;
-        const int grid = (int)(need < cap ? need : cap);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WG), 0, s, x, n, m, rows, g, Bs, post, X, pas, tab);
+        const int grid = slot_grid(rows, F, cap, true);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(WG), 0, s, x, n, m, rows, g, Bs, post, X, tb.pass, tb.tab);
     };
     if (real_in) go(k_czt_fused<P, true>, 1);
     else go(k_czt_fused<P, false>, 0);
@@ -219,14 +217,9 @@ bool czt_fused_supported(long long p) { return p >= 2 && p <= 4096 && (p & (p - 
 hipError_t launch_czt_fused(long long p, const void* x, int real_in, long long n, long long m, long long rows,
                             const float2* g, const float2* Bs, const float2* post, float2* X, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
-#define VVH_CZT(PP) \
-    case PP: return run_czt_fused<PP>(x, real_in, n, m, rows, g, Bs, post, X, s);
-    switch (p) {
-        VVH_CZT(2) VVH_CZT(4) VVH_CZT(8) VVH_CZT(16) VVH_CZT(32) VVH_CZT(64) VVH_CZT(128) VVH_CZT(256)
-        VVH_CZT(512) VVH_CZT(1024) VVH_CZT(2048) VVH_CZT(4096)
-        default: return hipErrorInvalidValue;
-    }
-#undef VVH_CZT
+    return pow2_dispatch<2, 4096>(p, [&](auto pp) {
+        return run_czt_fused<decltype(pp)::value>(x, real_in, n, m, rows, g, Bs, post, X, s);
+    });
 }
 
 }  // namespace vvh
@@ -304,16 +297,14 @@ bool ceps_fused_supported(long long n) { return n >= 2 && n <= 4096 && (n & (n -
 
 template <int N>
 static hipError_t run_ceps_fused(int kind, const float* x, long long rows, float* y, hipStream_t s) {
-    const float2* tab = twiddle_table(N);
-    const float2* pas = pass_twiddles(N);
-    if (!tab || !pas) return hipErrorOutOfMemory;
+    const Pow2Tables tb(N);
+    if (!tb.ok()) return hipErrorOutOfMemory;
     constexpr int WG = Wg<N>::value, F = Wg<N>::F;
     static std::atomic<int> capc[3];
     auto go = [&](auto kern, int k) {
         const int cap = cached_grid(capc[k], (const void*)kern, WG, 0, 1LL << 40);
-        const long long need = (rows + F - 1) / F;
-        const int grid = (int)(need < cap ? need : cap);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(WG), 0, s, x, rows, y, pas, tab);
+        const int grid = slot_grid(rows, F, cap, true);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(WG), 0, s, x, rows, y, tb.pass, tb.tab);
     };
     if (kind == 0) go(k_ceps_fused<N, 0>, 0);
     else if (kind == 1) go(k_ceps_fused<N, 1>, 1);
@@ -324,14 +315,7 @@ static hipError_t run_ceps_fused(int kind, const float* x, long long rows, float
 // kind 0 cepstrum, 1 icepstrum_minphase, 2 minphase_from_cepstrum (y complex[rows][n])
 hipError_t launch_ceps_fused(int kind, long long n, const float* x, long long rows, float* y, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
-#define VVH_CEPS(NN) \
-    case NN: return run_ceps_fused<NN>(kind, x, rows, y, s);
-    switch (n) {
-        VVH_CEPS(2) VVH_CEPS(4) VVH_CEPS(8) VVH_CEPS(16) VVH_CEPS(32) VVH_CEPS(64) VVH_CEPS(128) VVH_CEPS(256)
-        VVH_CEPS(512) VVH_CEPS(1024) VVH_CEPS(2048) VVH_CEPS(4096)
-        default: return hipErrorInvalidValue;
-    }
-#undef VVH_CEPS
+    return pow2_dispatch<2, 4096>(n, [&](auto nn) { return run_ceps_fused<decltype(nn)::value>(kind, x, rows, y, s); });
 }
 
 }  // namespace vvh

@@ -57,7 +57,7 @@ hipError_t launch_stft_mixed(long long nfft, long long hop, int kind, const floa
                              long long ch_stride, long long frames, const float* win, void* out,
                              long long out_ch_stride, hipStream_t s);
 // Real pow2 n = 2M above the fused kernels: split steps around an M-point C2C
-// (fft_kernels.hip).  fwd: Z [batch][M] -> X [batch][M+1]; inv: X -> V [batch][M].
+// (fft_glue.hip).  fwd: Z [batch][M] -> X [batch][M+1]; inv: X -> V [batch][M].
 hipError_t launch_real_split_fwd(const float2* Z, float2* X, long long M, long long batch, hipStream_t s);
 hipError_t launch_real_split_inv(const float2* X, float2* V, long long M, long long batch, hipStream_t s);
 // real[batch][n] -> complex[batch][n] (imaginary 0)
@@ -114,7 +114,7 @@ inline int capped_grid(std::atomic<int>& cache, const void* kern, int wg, long l
 // Blocks of a dynamic-walk launch (counters per XCD group): the same number in each of the 8 groups
 inline long long dyn_grid(int cap) { return cap / 8 * 8; }
 
-// ---- pow2 register/LDS FFTs (fft_kernels.hip) -----------------------------
+// ---- pow2 register/LDS FFTs (fft_c2c.hip, fft_real.hip; the naive DFT and glue: fft_glue.hip)
 bool c2c_supported(long long n);           // pow2, 2..4096
 // batch transforms of length n; element e of transform f at in[f*in_dist + e]
 hipError_t launch_c2c(long long n, int fwd, const float2* in, float2* out, long long batch,
@@ -435,7 +435,7 @@ hipError_t launch_savgol(const float* x, long long n, long long batch, long long
                          int mode, int policy, float* y, long long y_stride, int* flag, hipStream_t s);
 
 // ---- DCT / Hilbert helpers (spectral_kernels.hip) ----------------------
-// single-pass analytic signal / DCT-II (analytic_kernels.hip): rows [batch][n]
+// single-pass analytic signal / DCT-II (analytic_kernels.hip: hilbert_fused.hpp, dct2_fused.hpp): rows [batch][n]
 bool hilbert_fused_supported(long long n);
 hipError_t launch_hilbert_fused(long long n, const float* x, float2* z, long long batch, hipStream_t s);
 // instantaneous phase / frequency rows (phase_kernels.hip, hilbert.c:77-113)
