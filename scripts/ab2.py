@@ -206,6 +206,56 @@ def case_dct(L, s, n=1024, batch=131072):
         batch * n * 8, (lambda: y.clone())
 
 
+class PitchParams(C.Structure):
+    _fields_ = [(k, C.c_float) for k in ("sample_rate", "fmin", "fmax", "threshold")]
+
+
+def case_frames(L, s, kind, frame, hop, arg, nch=32, n=600 * 16000, center=0, rows=False):
+    """The per-frame features (kind lpc: arg = order; stats: arg = number of outputs, 7 =
+    the energy set; pitch: arg = (fmin, fmax, with cmnd)) of a Hamming-windowed signal
+    [nch][n] in one fused launch, or (rows) of nch * frames contiguous rows of `frame`
+    samples through the row entry point.  Outputs compare as int32 (bit for bit)."""
+    fr = (n + hop - 1) // hop if center else 1 + (n - frame) // hop
+    b = nch * fr
+    w = (0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(frame) / (frame - 1))).astype(np.float32)
+    x, win = buf((kind, frame, hop, nch, n, rows), lambda: (
+        torch.rand(b, frame, device="cuda") * 2 - 1 if rows else torch.rand(nch, n, device="cuda") * 2 - 1,
+        torch.from_numpy(w).cuda()))
+    head = (x.data_ptr(), n, nch, n, frame, hop, center, win.data_ptr())
+    if kind == "lpc":
+        out = buf(("lpc out", b, arg), lambda: torch.zeros(b * (arg + 2), device="cuda"))
+        a, err = out.data_ptr(), out.data_ptr() + 4 * b * (arg + 1)
+        L.vv_dsp_lpc_frames_device.argtypes = [vp, sz, sz, sz, sz, sz, C.c_int, vp, sz, vp, sz, vp, sz, vp]
+        L.vv_dsp_lpc_device.argtypes = [vp, sz, sz, sz, vp, vp, vp]
+        if rows:
+            run = lambda: ok(L, L.vv_dsp_lpc_device(x.data_ptr(), frame, arg, b, a, err, s), "lpc")  # noqa: E731
+        else:
+            run = lambda: ok(L, L.vv_dsp_lpc_frames_device(*head, arg, a, fr * (arg + 1), err, fr, s), "lpc_frames")  # noqa: E731
+    elif kind == "stats":
+        out = buf(("stats out", b), lambda: torch.zeros(12, b, device="cuda"))
+        energy = (3, 4, 5, 6, 9, 10, 11)   # rms min max crest zero_crossings argmin argmax
+        so = (vp * 12)(*[out[k].data_ptr() if arg == 12 or k in energy else None for k in range(12)])
+        L.vv_dsp_stats_frames_device.argtypes = [vp, sz, sz, sz, sz, sz, C.c_int, vp, vp, sz, vp]
+        L.vv_dsp_stats_device.argtypes = [vp, sz, sz, sz, vp, vp]
+        if rows:
+            run = lambda: ok(L, L.vv_dsp_stats_device(x.data_ptr(), frame, b, frame, so, s), "stats")  # noqa: E731
+        else:
+            run = lambda: ok(L, L.vv_dsp_stats_frames_device(*head, so, fr, s), "stats_frames")  # noqa: E731
+    else:
+        fmin, fmax, cmnd = arg
+        p = PitchParams(16000.0, fmin, fmax, 0.15)
+        curve = int(np.ceil(16000.0 / fmin)) + 1
+        out = buf(("pitch out", b, curve, cmnd), lambda: torch.zeros(b * (3 + (curve if cmnd else 0)), device="cuda"))
+        po = (vp * 4)(*[out.data_ptr() + 4 * b * k for k in range(3)], out.data_ptr() + 12 * b if cmnd else None)
+        L.vv_dsp_pitch_frames_device.argtypes = [vp, sz, sz, sz, sz, sz, C.c_int, vp, vp, vp, sz, sz, vp]
+        L.vv_dsp_pitch_device.argtypes = [vp, sz, sz, sz, vp, vp, sz, vp]
+        if rows:
+            run = lambda: ok(L, L.vv_dsp_pitch_device(x.data_ptr(), frame, b, frame, C.byref(p), po, curve, s), "pitch")  # noqa: E731
+        else:
+            run = lambda: ok(L, L.vv_dsp_pitch_frames_device(*head, C.byref(p), po, fr, fr * curve, s), "pitch_frames")  # noqa: E731
+    return run, 4 * x.numel(), (lambda: (out.view(torch.int32).clone(), out.zero_())[0])   # zeroed for the next build
+
+
 def burst(case, k):
     """k launches back to back per timed call (the per-launch time is ms / k)"""
     fn, byts, get = case
@@ -239,6 +289,18 @@ CASES = {
        for n in (256, 400, 512, 900, 960, 1024, 2000, 2048, 4096)},
     # power rows at the mixed-radix lengths (register kernel; 1000: the plan kernel)
     **{f"stftp{n}": (lambda L, s, n=n: case_stft_nfft(L, s, n, n // 4, power=True)) for n in (400, 960, 1000)},
+    # per-frame features: the workloads of lpcbench.py, statsbench.py and pitchbench.py, the row entry
+    # points, and one centred shape whose frames leave both ends of the signal
+    "lpc16k": lambda L, s: case_frames(L, s, "lpc", 400, 160, 16),
+    "lpc48k": lambda L, s: case_frames(L, s, "lpc", 1200, 480, 32, n=600 * 48000),
+    "statsenergy": lambda L, s: case_frames(L, s, "stats", 400, 160, 7),
+    "statsfull": lambda L, s: case_frames(L, s, "stats", 400, 160, 12),
+    "pitch400": lambda L, s: case_frames(L, s, "pitch", 400, 160, (100.0, 400.0, False)),
+    "pitch1024": lambda L, s: case_frames(L, s, "pitch", 1024, 256, (60.0, 500.0, False)),
+    **{k + "rows": (lambda L, s, k=k, a=a: case_frames(L, s, k, 400, 160, a, nch=8, rows=True))
+       for k, a in (("lpc", 16), ("stats", 12), ("pitch", (100.0, 400.0, False)))},
+    **{k + "edge": (lambda L, s, k=k, a=a: case_frames(L, s, k, 400, 160, a, nch=3, n=1000, center=1))
+       for k, a in (("lpc", 16), ("stats", 12), ("pitch", (100.0, 400.0, True)))},
 }
 
 

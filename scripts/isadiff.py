@@ -37,9 +37,11 @@ def assemble(src, tmp, hipcc, arch):
     return out
 
 
-def kernels(path):
+def kernels(path, rename=()):
     """{kernel: (instruction lines, descriptor lines)} of one assembly file"""
     text = subprocess.run(["c++filt"], input=open(path).read(), capture_output=True, text=True, check=True).stdout
+    for old, new in rename:
+        text = re.sub(r"\b%s\b" % re.escape(old), new, text)
     lines = text.replace("(anonymous namespace)::", "").split("\n")
     desc, cur = {}, None
     for ln in lines:   # descriptors first: they name the kernels
@@ -73,12 +75,12 @@ def kernels(path):
     return {k: (body.get(k, []), desc[k]) for k in desc}
 
 
-def side(paths, tmp, hipcc, arch):
+def side(paths, tmp, hipcc, arch, rename=()):
     with ThreadPoolExecutor(max_workers=8) as ex:
         asm = list(ex.map(lambda p: assemble(p, tmp, hipcc, arch) if p.endswith(".hip") else p, paths))
     allk, dup = {}, []
     for p, a in zip(paths, asm):
-        for k, v in kernels(a).items():
+        for k, v in kernels(a, rename).items():
             if k in allk:
                 dup.append((k, allk[k][2], p))
             allk[k] = (*v, p)
@@ -92,9 +94,11 @@ def main():
     ap.add_argument("--hipcc", default=os.path.join(os.environ.get("ROCM", "/opt/rocm"), "bin", "hipcc"))
     ap.add_argument("--arch", default="gfx950")
     ap.add_argument("-v", action="store_true", help="print the first differing line of each kernel")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW",
+                    help="a type renamed between the builds: OLD becomes NEW in side a's demangled names")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
-        A, dupa = side(args.a, tmp, args.hipcc, args.arch)
+        A, dupa = side(args.a, tmp, args.hipcc, args.arch, [r.split("=", 1) for r in args.rename])
         B, dupb = side(args.b, tmp, args.hipcc, args.arch)
     bad = 0
     for name, dup in (("a", dupa), ("b", dupb)):

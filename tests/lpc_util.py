@@ -20,6 +20,8 @@ import os
 
 import numpy as np
 
+from frames_util import hamming
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 CASES = [(1, 0), (2, 1), (33, 32), (64, 1), (65, 16), (320, 12), (400, 16), (1024, 32), (600, 128), (4100, 40)]
@@ -61,13 +63,6 @@ def make_signals(seed=20260):
                 acc -= den[j] * y[i - j]
         y[i] = acc
     return ((0.5 * w / np.abs(w).max()).astype(np.float32), (0.5 * y / np.abs(y).max()).astype(np.float32))
-
-
-def hamming(n):
-    """0.54 - 0.46 cos(2 pi i / (n - 1)) rounded to float32; ones for n = 1"""
-    if n == 1:
-        return np.ones(1, np.float32)
-    return (0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(n) / (n - 1))).astype(np.float32)
 
 
 def case_rows(white, resonant, n):

@@ -81,7 +81,7 @@ def num_frames(n, frame, hop, center):
 
 
 def reflect(idx, n):
-    """framing_index.hpp / framing.c:21-56"""
+    """frame_src.hpp / framing.c:21-56"""
     if idx < 0:
         a = -idx - 1
         if a >= n:

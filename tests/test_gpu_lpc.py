@@ -15,19 +15,17 @@ What is compared how:
   * lpspec against the f64 model with the exact residue (m k) mod nfft, bound
     max(2 x the reference's own error for that row, 2^-22) on the relative error.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import frames_util
 from conftest import tolerances
-from lpc_util import (LpcApi, CASES, GENERIC_CASES, WHITE_ROWS, SPEC_NFFT, SENTINEL, ERR_INTERNAL, OK, key, load,
-                      hamming)
+from frames_util import fetch_frames, hamming
+from lpc_util import (LpcApi, CASES, GENERIC_CASES, WHITE_ROWS, SPEC_NFFT, SENTINEL, ERR_INTERNAL, OK, key, load)
 
 pytestmark = pytest.mark.gpu
 
 FLOOR = 2.0 ** -22
-_vp, _sz = C.c_void_p, C.c_size_t
 
 
 @pytest.fixture(scope="module")
@@ -161,28 +159,9 @@ def test_host_calls_match_device_rows_and_reference_statuses(vdev, amd, cases):
 
 
 # ---------------------------------------------------------------- 4. fused frames
-def fetch_frames(vdev, ch, frame, hop, center, window):
-    """vv_dsp_fetch_frames_device of one contiguous channel -> (frames, frame)"""
-    import torch
-    L = vdev.lib()
-    L.vv_dsp_fetch_frames_device.argtypes = [_vp, _sz, _vp, _sz, _sz, _sz, _sz, C.c_int, _vp, _vp]
-    fr = vdev.num_frames(ch.numel(), frame, hop, center)
-    out = torch.empty((fr, frame), dtype=torch.float32, device=ch.device)
-    st = L.vv_dsp_fetch_frames_device(ch.data_ptr(), ch.numel(), out.data_ptr(), frame, hop, 0, fr, int(center),
-                                      None if window is None else window.data_ptr(),
-                                      torch.cuda.current_stream().cuda_stream)
-    assert st == OK
-    return out
-
-
 @pytest.fixture(scope="module")
 def three_channels(signals):
-    """(3, 16000) view of a (3, 16004) buffer: ch_stride 16004"""
-    import torch
-    buf = torch.zeros((3, 16004), dtype=torch.float32, device="cuda")
-    for i, s in enumerate((signals["white"], signals["resonant"], signals["white"][::-1].copy())):
-        buf[i, :16000] = torch.from_numpy(s).cuda()
-    return buf[:, :16000]
+    return frames_util.three_channels(signals["white"], signals["resonant"])
 
 
 @pytest.mark.parametrize("windowed", [0, 1])

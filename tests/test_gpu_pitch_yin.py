@@ -21,12 +21,12 @@ import numpy as np
 import pytest
 
 import pitch_util as pu
+from frames_util import fetch_frames
 from pitch_util import CASES, CASE_IDS, BATCH, SENTINEL, OK, f32_ulps
 
 pytestmark = pytest.mark.gpu
 
 NAMES = ("f0", "aperiodicity", "lag", "cmnd")
-_vp, _sz = C.c_void_p, C.c_size_t
 POISON = float("nan")
 
 
@@ -107,20 +107,6 @@ def test_frames_against_model(vdev, counter, i):
 
 
 # ---------------------------------------------------------------- 2. bit for bit against each other
-def fetch_frames(vdev, ch, frame, hop, center, window):
-    """vv_dsp_fetch_frames_device of one contiguous channel -> (frames, frame)"""
-    import torch
-    L = vdev.lib()
-    L.vv_dsp_fetch_frames_device.argtypes = [_vp, _sz, _vp, _sz, _sz, _sz, _sz, C.c_int, _vp, _vp]
-    fr = vdev.num_frames(ch.numel(), frame, hop, center)
-    out = torch.empty((fr, frame), dtype=torch.float32, device=ch.device)
-    st = L.vv_dsp_fetch_frames_device(ch.data_ptr(), ch.numel(), out.data_ptr(), frame, hop, 0, fr, int(center),
-                                      None if window is None else window.data_ptr(),
-                                      torch.cuda.current_stream().cuda_stream)
-    assert st == OK
-    return out
-
-
 @pytest.mark.parametrize("i", range(len(CASES)), ids=CASE_IDS)
 def test_frames_is_the_pipeline(vdev, i):
     """pitch_frames_device == fetch_frames_device -> pitch_device, also with ch_stride > n"""

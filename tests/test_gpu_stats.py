@@ -21,13 +21,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import frames_util
+from frames_util import fetch_frames, hamming
 from stats_util import (StatsApi, STAT_NAMES, COUNT_NAMES, EXACT_NAMES, F64_NAMES, ENERGY_NAMES, MIN_LEN, ROW_N, BATCH,
                         SLICES, CHUNK, LONG_N, AUTO_CASES, CROSS_CASES, EDGE_N, SENTINEL, ERR_SIZE, OK, load,
                         signals, valid_names, batch_rows, long_row, edge_rows, f32_ulps)
 
 pytestmark = pytest.mark.gpu
 
-_vp, _sz = C.c_void_p, C.c_size_t
 
 
 @pytest.fixture(scope="module")
@@ -246,35 +247,9 @@ def test_host_calls_equal_the_batch_row(vdev, amd):
 
 
 # ---------------------------------------------------------------- 4. frames
-def fetch_frames(vdev, ch, frame, hop, center, window):
-    """vv_dsp_fetch_frames_device of one contiguous channel -> (frames, frame)"""
-    import torch
-    L = vdev.lib()
-    L.vv_dsp_fetch_frames_device.argtypes = [_vp, _sz, _vp, _sz, _sz, _sz, _sz, C.c_int, _vp, _vp]
-    fr = vdev.num_frames(ch.numel(), frame, hop, center)
-    out = torch.empty((fr, frame), dtype=torch.float32, device=ch.device)
-    st = L.vv_dsp_fetch_frames_device(ch.data_ptr(), ch.numel(), out.data_ptr(), frame, hop, 0, fr, int(center),
-                                      None if window is None else window.data_ptr(),
-                                      torch.cuda.current_stream().cuda_stream)
-    assert st == OK
-    return out
-
-
 @pytest.fixture(scope="module")
 def three_channels():
-    """(3, 16000) view of a (3, 16004) buffer: ch_stride 16004"""
-    import torch
-    white, resonant = signals()
-    buf = torch.zeros((3, 16004), dtype=torch.float32, device="cuda")
-    for i, s in enumerate((white, resonant, white[::-1].copy())):
-        buf[i, :16000] = torch.from_numpy(s).cuda()
-    return buf[:, :16000]
-
-
-def hamming(n):
-    if n == 1:
-        return np.ones(1, np.float32)
-    return (0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(n) / (n - 1))).astype(np.float32)
+    return frames_util.three_channels(*signals())
 
 
 @pytest.mark.parametrize("windowed", [0, 1])

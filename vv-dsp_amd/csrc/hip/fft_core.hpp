@@ -31,6 +31,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "wave_sync.hpp"
+
 #include <cstdint>
 #include <type_traits>
 
@@ -444,7 +446,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 // Barrier between LDS writes and reads of one transform.  A transform owned by
 // threads of a single wave needs no s_barrier: LDS ops of a wave execute in
-// order; only the compiler must not move them (wave_barrier + fence).
+// order; only the compiler must not move them (wave_sync, wave_sync.hpp).
 // No memory fences: a fence makes hipcc drain vmcnt (outstanding global loads
 // AND stores) at every exchange, which serialises the streaming pipeline.  LDS
 // ordering needs only lgkmcnt + s_barrier across waves, and nothing but a
@@ -454,9 +456,7 @@ __device__ __forceinline__ void xsync() {
     if constexpr (T > 64) {
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     } else {
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("" ::: "memory");
+        wave_sync();
     }
 }
 

@@ -5,11 +5,11 @@
 // Both are HBM-bound data movement (4 B read + 4 B written per frame sample;
 // overlapping frames re-read the signal from L2).  Results are bit-identical
 // to the reference loops: the gather is a copy (times the window, one
-// rounded multiply), and the overlap-add sums each output sample's
+// rounded multiply: frame_sample, frame_src.hpp, which the fused per-frame
+// kernels read through as well), and the overlap-add sums each output sample's
 // contributions in increasing frame order, the order of a caller's loop over
 // frame_index.
-#include "framing_index.hpp"
-#include "vvhip_internal.hpp"
+#include "frame_src.hpp"
 
 namespace vvh {
 
@@ -20,17 +20,16 @@ __global__ void __launch_bounds__(256) k_fetch_frames(const float* __restrict__ 
                                                       float* __restrict__ out, long long len, long long hop,
                                                       long long frame0, long long count, int center,
                                                       const float* __restrict__ win) {
+    FrameSrc src;   // what frame_sample reads of it
+    src.sig_n = n;
+    src.center = center;
+    src.win = win;
     const long long total = count * len;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
          e += (long long)gridDim.x * blockDim.x) {
         const long long f = e / len, i = e - f * len;
         const long long start = (frame0 + f) * hop - (center ? len / 2 : 0);
-        const long long k = start + i;
-        float v;
-        if (center) v = sig[reflect_index(k, n) - base];
-        else v = (k < 0 || k >= n) ? 0.0f : sig[k - base];
-        if (win) v = v * win[i];
-        __builtin_nontemporal_store(v, out + e);
+        __builtin_nontemporal_store(frame_sample<false>(src, sig, start, i, base), out + e);
     }
 }
 

@@ -3,9 +3,9 @@
 // src/envelope/lpc.c, over rows or over the frames of a signal.
 //
 // Autocorrelation, wave kernel (order <= 32, row length <= 4096).  One wave
-// takes one row.  The row (a frame: gathered and windowed exactly as
-// k_fetch_frames does) goes to LDS; lane l owns samples [l C, (l + 1) C),
-// C = the row length over 64 rounded up to a multiple of 8, and walks them in
+// takes one row.  The row (of a FrameSrc: a frame is read through frame_sample,
+// frame_src.hpp, as k_fetch_frames reads it) goes to LDS; lane l owns samples
+// [l C, (l + 1) C), C = the row length over 64 rounded up to a multiple of 8, and walks them in
 // tiles of 8: one tile is 8 + P samples read as float4 (P = 16 or 32, the
 // template's order bound) and 8 (P + 1) FMAs from registers, 0.15 LDS floats
 // per FMA at P = 32.  Samples past the row's end are stored as zeros, so their
@@ -33,56 +33,17 @@
 //
 // Generic kernels (any order < row length): one workgroup per autocorrelation
 // row, lag by lag; one thread per Levinson row working in the output row.
-#include "framing_index.hpp"
-#include "vvhip_internal.hpp"
+#include "frame_src.hpp"
+#include "wave_sync.hpp"
 
 namespace vvh {
 
 namespace {
 
-struct LpcRow {
-    const float* p;
-    long long start;
-};
-
-// row = frame f of channel ch
-__device__ __forceinline__ LpcRow lpc_row(const LpcSrc& s, long long row, long long ch, long long f) {
-    if (!s.framed) return {s.x + row * s.len, 0};
-    return {s.x + ch * s.ch_stride, f * s.hop - (s.center ? s.len / 2 : 0)};
-}
-
-__device__ __forceinline__ LpcRow lpc_row(const LpcSrc& s, long long row) {
-    const long long ch = s.framed ? row / s.frames : 0;
-    return lpc_row(s, row, ch, row - ch * s.frames);
-}
-
-// sample i of the row: k_fetch_frames' value (framing_kernels.hip) for a frame
-__device__ __forceinline__ float lpc_sample(const LpcSrc& s, const LpcRow& r, long long i) {
-    if (!s.framed) return r.p[i];
-    const long long k = r.start + i;
-    float v;
-    if (s.center) v = r.p[reflect_index(k, s.sig_n)];
-    else v = (k < 0 || k >= s.sig_n) ? 0.0f : r.p[k];
-    if (s.win) v = v * s.win[i];
-    return v;
-}
-
-// a row whose samples are all inside the signal: sample i is r.p[r.start + i] (times the window)
-__device__ __forceinline__ bool lpc_row_inside(const LpcSrc& s, const LpcRow& r) {
-    return !s.framed || (r.start >= 0 && r.start + s.len <= s.sig_n);
-}
-
 __device__ __forceinline__ float* lpc_out_row(const LpcOut& o, long long row, int order, float** err) {
     const long long ch = row / o.frames, f = row - ch * o.frames;
     *err = o.err + ch * o.err_ch_stride + f;
     return o.a + ch * o.a_ch_stride + f * (order + 1);
-}
-
-// LDS ops of one wave execute in order; only the compiler must not move them
-__device__ __forceinline__ void wave_sync() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
 }
 
 // four consecutive floats at any 4-byte-aligned address as one load (a frame
@@ -146,7 +107,7 @@ __device__ __forceinline__ void levinson_store(const float (&r)[P + 1], int orde
 // 64 rows per workgroup, 16 per wave.  Dynamic LDS: r rows [64][P + 1], then one
 // buffer of wbuf floats per wave (the row's image, then the transpose).
 template <int P>
-__global__ void __launch_bounds__(256) k_lpc_wave(LpcSrc src, int order, int C, int wbuf, float* __restrict__ r_out,
+__global__ void __launch_bounds__(256) k_lpc_wave(FrameSrc src, int order, int C, int wbuf, float* __restrict__ r_out,
                                                   LpcOut out) {
     extern __shared__ float4 lpc_lds4[];
     constexpr int RS = P + 1;            // odd: 64 lanes read 64 rows conflict-free
@@ -179,7 +140,7 @@ __global__ void __launch_bounds__(256) k_lpc_wave(LpcSrc src, int order, int C, 
             fr -= src.frames;
             ++ch;
         }
-        const LpcRow rw = lpc_row(src, row, ch, fr);
+        const FrameRow<> rw = frame_row(src, row, ch, fr);
         wave_sync();                     // the previous row's transpose has been read
         // A row inside the signal and at least a chunk long (every row of a batch,
         // every frame but the few at the ends): a lane loads its own chunk, 8
@@ -188,7 +149,7 @@ __global__ void __launch_bounds__(256) k_lpc_wave(LpcSrc src, int order, int C, 
         // float4 stores with no index arithmetic.  A lane whose chunk passes the
         // row's end stores zeros (it loads from the row's start, a valid place);
         // the one lane the end falls inside then adds its few samples one by one.
-        if (lpc_row_inside(src, rw) && n >= C) {
+        if (rw.inside && n >= C) {
             const bool full = lane * C + C <= n;
             const float* fp = rw.p + rw.start + (full ? lane * C : 0);
             const float* wp = src.win + (full ? lane * C : 0);
@@ -217,11 +178,11 @@ __global__ void __launch_bounds__(256) k_lpc_wave(LpcSrc src, int order, int C, 
             }
             if (lane < P) xb[zoff] = 0.0f;           // the look-ahead past the last chunk
             if (!full && lane * C < n)               // the chunk the row ends in
-                for (int i = lane * C; i < n; ++i) xw[i - lane * C] = lpc_sample(src, rw, i);
+                for (int i = lane * C; i < n; ++i) xw[i - lane * C] = frame_sample<true>(src, rw, i);
         } else {
             int q = lq, rem = lr;
             for (int i = lane; i < total; i += 64) {
-                xb[i + 4 * q] = i < n ? lpc_sample(src, rw, i) : 0.0f;
+                xb[i + 4 * q] = i < n ? frame_sample(src, rw, i) : 0.0f;
                 q += dq;
                 rem += dr;
                 if (rem >= C) {
@@ -339,15 +300,15 @@ __global__ void __launch_bounds__(64) k_levinson_generic(const float* __restrict
 
 // one workgroup per row: thread t adds the products of samples t, t + 256, ...
 // of lag k, then a fixed tree over the 256 partial sums
-__global__ void __launch_bounds__(256) k_autocorr_generic(LpcSrc src, long long order, float* __restrict__ r_out) {
+__global__ void __launch_bounds__(256) k_autocorr_generic(FrameSrc src, long long order, float* __restrict__ r_out) {
     __shared__ float red[256];
     const long long row = blockIdx.x;
-    const LpcRow rw = lpc_row(src, row);
+    const FrameRow<> rw = frame_row(src, row);
     const int t = threadIdx.x;
     for (long long k = 0; k <= order; ++k) {
         float s = 0.0f;
         for (long long i = t; i < src.len - k; i += 256)
-            s = __builtin_fmaf(lpc_sample(src, rw, i), lpc_sample(src, rw, i + k), s);
+            s = __builtin_fmaf(frame_sample(src, rw, i), frame_sample(src, rw, i + k), s);
         red[t] = s;
         __syncthreads();
         for (int h = 128; h > 0; h >>= 1) {
@@ -420,7 +381,7 @@ constexpr size_t LPSPEC_TABLE_BYTES = 64u << 10;
 
 }  // namespace
 
-hipError_t launch_lpc_wave(const LpcSrc& src, int order, float* r, const LpcOut& out, hipStream_t s) {
+hipError_t launch_lpc_wave(const FrameSrc& src, int order, float* r, const LpcOut& out, hipStream_t s) {
     if (src.rows <= 0) return hipSuccess;
     if (!lpc_wave_supported(src.len, order)) return hipErrorInvalidValue;
     const long long blocks = (src.rows + 63) / 64;
@@ -442,7 +403,7 @@ hipError_t launch_lpc_wave(const LpcSrc& src, int order, float* r, const LpcOut&
     return hipGetLastError();
 }
 
-hipError_t launch_autocorr_generic(const LpcSrc& src, long long order, float* r, hipStream_t s) {
+hipError_t launch_autocorr_generic(const FrameSrc& src, long long order, float* r, hipStream_t s) {
     if (src.rows <= 0) return hipSuccess;
     if (src.rows > 0x7fffffffLL || order >= src.len) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_autocorr_generic, dim3((unsigned)src.rows), dim3(256), 0, s, src, order, r);

@@ -3,11 +3,11 @@
 // signal.  include/vv_dsp/features/pitch.h states the definition; this file
 // states how it is computed.
 //
-// One wave per row.  The row (a frame gathered as k_fetch_frames gathers it:
-// zero padding, reflection when centred, one rounded multiply by the window)
-// goes to the wave's own piece of LDS once, as f64 where four rows of f64 fit
-// 64 KiB (the conversion is exact, so both storages give the same bits) and as
-// f32 beyond.  No workgroup barrier is needed: a wave reads only what it wrote.
+// One wave per row.  The row (of a FrameSrc: a frame is read through
+// frame_sample, frame_src.hpp, as k_fetch_frames reads it) goes to the wave's
+// own piece of LDS once, as f64 where four rows of f64 fit 64 KiB (the
+// conversion is exact, so both storages give the same bits) and as f32 beyond.
+// No workgroup barrier is needed: a wave reads only what it wrote.
 //
 // Difference function.  Lane l owns T adjacent lags t0 = base + T l .. t0 + T - 1
 // and walks j = 0 .. W - 1 in runs of R = PITCH_RUN: a run loads x[j .. j + R) (the
@@ -26,8 +26,8 @@
 // lanes whose right neighbour is not smaller, the unvoiced minimum a per-lane
 // strictly-smaller scan in ascending tau and an xor butterfly on (value, lag)
 // that prefers the lower lag at equal values.
-#include "framing_index.hpp"
-#include "vvhip_internal.hpp"
+#include "frame_src.hpp"
+#include "wave_sync.hpp"
 
 #include <climits>
 #include <cmath>
@@ -39,42 +39,17 @@ namespace {
 constexpr int PITCH_RUN = 8;                     // R: consecutive j per load group
 constexpr size_t PITCH_LDS_SMALL = 64u << 10;    // dynamic LDS a launch gets without asking
 
-struct PitchRow {
-    const float* p;
-    long long start;
-    bool inside;          // every sample is p[start + i] (times the window)
-    long long at, at_c;   // where the row's values go in the planes / in cmnd
+struct PitchAt {
+    long long plane, cmnd;   // where the row's values go in the planes / in cmnd
 };
+using PitchRow = FrameRow<PitchAt>;
 
-// rows and frames are below 2^31: the (channel, frame) split is a 32-bit division
-__device__ __forceinline__ PitchRow pitch_row(const StatsSrc& s, const PitchOut& o, long long row) {
-    if (!s.framed) return {s.x + row * s.row_stride, 0, true, row, row * o.cmnd_row_stride};
-    const unsigned ch = (unsigned)row / (unsigned)s.frames, f = (unsigned)row - ch * (unsigned)s.frames;
-    const long long start = (long long)f * s.hop - (s.center ? s.len / 2 : 0);
-    return {s.x + ch * s.ch_stride, start, start >= 0 && start + s.len <= s.sig_n, ch * o.ch_stride + f,
-            ch * o.cmnd_ch_stride + f * o.cmnd_row_stride};
-}
-
-// sample i of the row: k_fetch_frames' value (framing_kernels.hip) for a frame
-template <bool INSIDE>
-__device__ __forceinline__ float pitch_sample(const StatsSrc& s, const PitchRow& r, int i) {
-    float v;
-    if (INSIDE) {
-        v = r.p[r.start + i];
-    } else {
-        const long long k = r.start + i;
-        if (s.center) v = r.p[reflect_index(k, s.sig_n)];
-        else v = (k < 0 || k >= s.sig_n) ? 0.0f : r.p[k];
-    }
-    if (s.win) v = v * s.win[i];
-    return v;
-}
-
-// LDS traffic of one wave: its lanes' stores are complete before its lanes' loads
-__device__ __forceinline__ void wave_sync() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
+__device__ __forceinline__ PitchRow pitch_row(const FrameSrc& s, const PitchOut& o, long long row) {
+    return frame_row(
+        s, row, [&] { return PitchAt{row, row * o.cmnd_row_stride}; },
+        [&](unsigned ch, unsigned f) {
+            return PitchAt{ch * o.ch_stride + f, ch * o.cmnd_ch_stride + f * o.cmnd_row_stride};
+        });
 }
 
 // The run x[j .. j + R): j is a multiple of R and the row 16-byte aligned, so it
@@ -218,27 +193,27 @@ __device__ __forceinline__ PitchResult pitch_decide(const double* __restrict__ q
 }
 
 template <int T, class S, bool INSIDE>
-__device__ __forceinline__ void pitch_wave_row(const StatsSrc& src, const PitchRow& rw, const PitchCfg& cfg,
+__device__ __forceinline__ void pitch_wave_row(const FrameSrc& src, const PitchRow& rw, const PitchCfg& cfg,
                                                const PitchOut& out, S* xs, double* d, int lane) {
     const int n = (int)src.len;
-    for (int i = lane; i < n; i += 64) xs[i] = (S)pitch_sample<INSIDE>(src, rw, i);
+    for (int i = lane; i < n; i += 64) xs[i] = (S)frame_sample<INSIDE>(src, rw, i);
     wave_sync();
     pitch_difference<T, S>(xs, d, cfg.tau_max, cfg.W, lane);
     wave_sync();
-    const double total = pitch_cmnd(d, cfg.tau_max, out.cmnd ? out.cmnd + rw.at_c : nullptr, lane);
+    const double total = pitch_cmnd(d, cfg.tau_max, out.cmnd ? out.cmnd + rw.at.cmnd : nullptr, lane);
     wave_sync();
     PitchResult r = {0.0f, NAN, 0u};   // a non-finite sample: c(tau_max) holds every one of them
     if (isfinite(total)) r = pitch_decide(d, cfg, lane);
     if (lane == 0) {
-        if (out.f0) out.f0[rw.at] = r.f0;
-        if (out.aperiodicity) out.aperiodicity[rw.at] = r.ap;
-        if (out.lag) out.lag[rw.at] = r.lag;
+        if (out.f0) out.f0[rw.at.plane] = r.f0;
+        if (out.aperiodicity) out.aperiodicity[rw.at.plane] = r.ap;
+        if (out.lag) out.lag[rw.at.plane] = r.lag;
     }
 }
 
 // one wave per row, wpb rows per workgroup; row_bytes of LDS per wave: the row, then d
 template <int T, class S>
-__global__ void __launch_bounds__(256) k_pitch(StatsSrc src, PitchCfg cfg, PitchOut out, int wpb, int x_bytes,
+__global__ void __launch_bounds__(256) k_pitch(FrameSrc src, PitchCfg cfg, PitchOut out, int wpb, int x_bytes,
                                                int row_bytes) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pitch_lds[];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -254,7 +229,7 @@ __global__ void __launch_bounds__(256) k_pitch(StatsSrc src, PitchCfg cfg, Pitch
 }
 
 template <int T, class S>
-hipError_t pitch_launch(const StatsSrc& src, const PitchCfg& cfg, const PitchOut& out, hipStream_t s) {
+hipError_t pitch_launch(const FrameSrc& src, const PitchCfg& cfg, const PitchOut& out, hipStream_t s) {
     const size_t x_bytes = ((size_t)src.len * sizeof(S) + 15) / 16 * 16;
     const size_t row_bytes = x_bytes + ((size_t)(cfg.tau_max + 1) * sizeof(double) + 15) / 16 * 16;
     size_t wpb = PITCH_LDS_SMALL / row_bytes;
@@ -274,7 +249,7 @@ hipError_t pitch_launch(const StatsSrc& src, const PitchCfg& cfg, const PitchOut
 
 }  // namespace
 
-hipError_t launch_pitch(const StatsSrc& src, const PitchCfg& cfg, const PitchOut& out, bool f32_rows, hipStream_t s) {
+hipError_t launch_pitch(const FrameSrc& src, const PitchCfg& cfg, const PitchOut& out, bool f32_rows, hipStream_t s) {
     if (src.rows <= 0 || !out.any()) return hipSuccess;
     if (src.len <= 0 || src.len > PITCH_MAX_FRAME || src.rows >= (1LL << 31) || src.frames <= 0 || cfg.tau_min < 2 ||
         cfg.tau_min >= cfg.tau_max || cfg.tau_max > PITCH_MAX_LAG || cfg.W < 1 ||

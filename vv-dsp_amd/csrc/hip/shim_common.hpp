@@ -262,6 +262,57 @@ private:
     }
 };
 
+// ---- the rows of a per-frame entry point (shim_lpc / shim_stats / shim_pitch):
+// the FrameSrc (vvhip_internal.hpp) of `batch` rows of n samples ...
+inline FrameSrc rows_src(const float* d_x, size_t n, size_t batch, size_t row_stride) {
+    FrameSrc src;
+    src.x = d_x;
+    src.len = (long long)n;
+    src.rows = src.frames = (long long)batch;
+    src.row_stride = (long long)row_stride;
+    return src;
+}
+// ... and of the frames of nch channels of signal [nch][n]
+inline FrameSrc frames_src(const float* d_signal, size_t n, size_t nch, size_t ch_stride, size_t frame_len,
+                           size_t hop, size_t frames, int center, const float* d_window) {
+    FrameSrc src;
+    src.x = d_signal;
+    src.len = (long long)frame_len;
+    src.frames = (long long)frames;
+    src.rows = (long long)(nch * frames);
+    src.sig_n = (long long)n;
+    src.ch_stride = (long long)ch_stride;
+    src.hop = (long long)hop;
+    src.framed = 1;
+    src.center = center != 0;
+    src.win = d_window;
+    return src;
+}
+// The size checks of the framed entry point `who`, in the order every one of
+// them makes them; an entry point's own checks stand between the steps, and
+// that order is part of its contract (statuses are asserted by the tests).
+struct FramesCall {
+    const char* who;
+    size_t n, nch, frame_len, hop, frames;
+    // first, after the null pointers
+    int shape() const { return hop == 0 || frame_len == 0 ? ST_SIZE : ST_OK; }
+    // what one call and FrameSrc's 32-bit row split take
+    int limits() const {
+        if (frame_len >= ((size_t)1 << 32) || n >= ((size_t)1 << 40) || nch >= ((size_t)1 << 31) ||
+            frames >= ((size_t)1 << 31) || nch * frames >= ((size_t)1 << 31))
+            return fail(ST_SIZE, (std::string(who) + ": too many frames for one call").c_str());
+        return ST_OK;
+    }
+    // last: true when there are rows to launch, else *st is what the call returns
+    bool start(int* st) const {
+        *st = ST_OK;
+        if (device_count() <= 0) *st = fail(ST_UNSUP, "no HIP device");
+        else if (frames == 0 || nch == 0) return false;
+        else if (n == 0) *st = ST_SIZE;   // frames of an empty signal (center): nothing to reflect
+        return *st == ST_OK;
+    }
+};
+
 // ---- shim_fft.hip: the FFT dispatch every other module transforms through ----
 // Non-power-of-two DFT: the mixed-radix kernel for 7-smooth n <= 4096, else the
 // exact-angle f64 O(n^2) kernel for short lengths and Bluestein over the

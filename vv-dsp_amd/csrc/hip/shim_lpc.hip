@@ -11,13 +11,8 @@ static bool lpc_generic(long long len, long long order) {
     return knob(KNOB_LPC_GENERIC, 0) == 1 || !lpc_wave_supported(len, order);
 }
 
-static LpcSrc lpc_rows(const float* d_x, size_t n, size_t batch) {
-    LpcSrc src;
-    src.x = d_x;
-    src.len = (long long)n;
-    src.rows = src.frames = (long long)batch;
-    return src;
-}
+// contiguous rows
+static FrameSrc lpc_rows(const float* d_x, size_t n, size_t batch) { return rows_src(d_x, n, batch, n); }
 
 static LpcOut lpc_rows_out(float* d_a, float* d_err, size_t batch, int* d_flag) {
     LpcOut out;
@@ -29,7 +24,7 @@ static LpcOut lpc_rows_out(float* d_a, float* d_err, size_t batch, int* d_flag) 
 }
 
 // autocorrelation + Levinson of src's rows
-static int lpc_run(const LpcSrc& src, size_t order, const LpcOut& out, hipStream_t s) {
+static int lpc_run(const FrameSrc& src, size_t order, const LpcOut& out, hipStream_t s) {
     if (!lpc_generic(src.len, (long long)order)) {
         HIPCHK(launch_lpc_wave(src, (int)order, nullptr, out, s), ST_INTERNAL);
         stat_inc(STAT_LPC_WAVE);
@@ -56,7 +51,7 @@ int vvhip_autocorr_device(const float* d_x, size_t n, size_t order, size_t batch
     if (int st = lpc_sizes(n, order, batch)) return st;
     if (device_count() <= 0) return fail(ST_UNSUP, "no HIP device");
     if (batch == 0) return ST_OK;
-    const LpcSrc src = lpc_rows(d_x, n, batch);
+    const FrameSrc src = lpc_rows(d_x, n, batch);
     if (!lpc_generic(src.len, (long long)order)) {
         HIPCHK(launch_lpc_wave(src, (int)order, d_r, LpcOut(), (hipStream_t)stream), ST_INTERNAL);
         stat_inc(STAT_LPC_WAVE);
@@ -95,32 +90,20 @@ int vvhip_lpc_frames_device(const float* d_signal, size_t n, size_t nch, size_t 
                             size_t hop, size_t frames, int center, const float* d_window, size_t order, float* d_a,
                             size_t a_ch_stride, float* d_err, size_t err_ch_stride, void* stream) {
     if (!d_signal || !d_a || !d_err) return ST_NULL;
-    if (hop == 0 || frame_len == 0) return ST_SIZE;
+    const FramesCall fc = {"lpc_frames", n, nch, frame_len, hop, frames};
+    if (int st = fc.shape()) return st;
     if (int st = lpc_sizes(frame_len, order, 0)) return st;
-    if (n >= ((size_t)1 << 40) || nch >= ((size_t)1 << 31) || frames >= ((size_t)1 << 31) ||
-        nch * frames >= ((size_t)1 << 31))
-        return fail(ST_SIZE, "lpc_frames: too many frames for one call");
-    if (device_count() <= 0) return fail(ST_UNSUP, "no HIP device");
-    if (frames == 0 || nch == 0) return ST_OK;
-    if (n == 0) return ST_SIZE;   // frames of an empty signal (center): nothing to reflect
-    LpcSrc src;
-    src.x = d_signal;
-    src.len = (long long)frame_len;
-    src.frames = (long long)frames;
-    src.rows = (long long)(nch * frames);
-    src.sig_n = (long long)n;
-    src.ch_stride = (long long)ch_stride;
-    src.hop = (long long)hop;
-    src.framed = 1;
-    src.center = center != 0;
-    src.win = d_window;
+    if (int st = fc.limits()) return st;
+    int st;
+    if (!fc.start(&st)) return st;
     LpcOut out;
     out.a = d_a;
     out.err = d_err;
     out.frames = (long long)frames;
     out.a_ch_stride = (long long)a_ch_stride;
     out.err_ch_stride = (long long)err_ch_stride;
-    return lpc_run(src, order, out, (hipStream_t)stream);
+    return lpc_run(frames_src(d_signal, n, nch, ch_stride, frame_len, hop, frames, center, d_window), order, out,
+                   (hipStream_t)stream);
 }
 
 int vvhip_lpspec_device(const float* d_a, size_t order, const float* d_gain, float gain, size_t nfft, size_t batch,

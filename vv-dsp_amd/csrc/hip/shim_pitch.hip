@@ -45,7 +45,7 @@ static PitchOut pitch_out(const vvhip_pitch_out* o) {
     return out;
 }
 
-static int pitch_run(const StatsSrc& src, const PitchCfg& cfg, const PitchOut& out, hipStream_t s) {
+static int pitch_run(const FrameSrc& src, const PitchCfg& cfg, const PitchOut& out, hipStream_t s) {
     HIPCHK(launch_pitch(src, cfg, out, knob(KNOB_PITCH_F32, 0) == 1, s), ST_INTERNAL);
     stat_inc(STAT_PITCH_WAVE);
     return ST_OK;
@@ -79,12 +79,7 @@ int vvhip_pitch_device(const float* d_x, size_t n, size_t batch, size_t row_stri
     if (device_count() <= 0) return fail(ST_UNSUP, "no HIP device");
     if (batch == 0) return ST_OK;
     out.cmnd_row_stride = (long long)cmnd_row_stride;
-    StatsSrc src;
-    src.x = d_x;
-    src.len = (long long)n;
-    src.rows = src.frames = (long long)batch;
-    src.row_stride = (long long)row_stride;
-    return pitch_run(src, cfg, out, (hipStream_t)stream);
+    return pitch_run(rows_src(d_x, n, batch, row_stride), cfg, out, (hipStream_t)stream);
 }
 
 int vvhip_pitch_frames_device(const float* d_signal, size_t n, size_t nch, size_t ch_stride, size_t frame_len,
@@ -92,37 +87,24 @@ int vvhip_pitch_frames_device(const float* d_signal, size_t n, size_t nch, size_
                               const vvhip_pitch_params* params, const vvhip_pitch_out* o, size_t out_ch_stride,
                               size_t cmnd_ch_stride, void* stream) {
     if (!d_signal || !params || !o) return ST_NULL;
-    if (hop == 0 || frame_len == 0) return ST_SIZE;
+    const FramesCall fc = {"pitch_frames", n, nch, frame_len, hop, frames};
+    if (int st = fc.shape()) return st;
     PitchCfg cfg;
-    const int st = pitch_range(params, frame_len, &cfg);
-    if (st != ST_OK) return st;
+    if (int st = pitch_range(params, frame_len, &cfg)) return st;
     PitchOut out = pitch_out(o);
     if (!out.any()) return ST_OK;
-    if (n >= ((size_t)1 << 40) || nch >= ((size_t)1 << 31) || frames >= ((size_t)1 << 31) ||
-        nch * frames >= ((size_t)1 << 31))
-        return fail(ST_SIZE, "pitch_frames: too many frames for one call");
+    if (int st = fc.limits()) return st;
     const size_t curve = (size_t)cfg.tau_max + 1;
     if (nch > 1 && (ch_stride < n || ((out.f0 || out.aperiodicity || out.lag) && out_ch_stride < frames) ||
                     (out.cmnd && cmnd_ch_stride < frames * curve)))
         return fail(ST_SIZE, "pitch_frames: a channel stride shorter than its channel");
-    if (device_count() <= 0) return fail(ST_UNSUP, "no HIP device");
-    if (frames == 0 || nch == 0) return ST_OK;
-    if (n == 0) return ST_SIZE;   // frames of an empty signal (center): nothing to reflect
+    int st;
+    if (!fc.start(&st)) return st;
     out.ch_stride = (long long)out_ch_stride;
     out.cmnd_ch_stride = (long long)cmnd_ch_stride;
     out.cmnd_row_stride = (long long)curve;
-    StatsSrc src;
-    src.x = d_signal;
-    src.len = (long long)frame_len;
-    src.frames = (long long)frames;
-    src.rows = (long long)(nch * frames);
-    src.sig_n = (long long)n;
-    src.ch_stride = (long long)ch_stride;
-    src.hop = (long long)hop;
-    src.framed = 1;
-    src.center = center != 0;
-    src.win = d_window;
-    return pitch_run(src, cfg, out, (hipStream_t)stream);
+    return pitch_run(frames_src(d_signal, n, nch, ch_stride, frame_len, hop, frames, center, d_window), cfg, out,
+                     (hipStream_t)stream);
 }
 
 // One frame in host memory through the same kernel; either output may be null.

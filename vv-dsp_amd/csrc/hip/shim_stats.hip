@@ -30,7 +30,7 @@ static StatsOut stats_out(const vvhip_stats_out* o, size_t ch_stride) {
     return out;
 }
 
-static int stats_run(const StatsSrc& src, const StatsOut& out, hipStream_t s) {
+static int stats_run(const FrameSrc& src, const StatsOut& out, hipStream_t s) {
     if (!stats_long(src.len)) {
         HIPCHK(launch_stats_wave(src, out, s), ST_INTERNAL);
         stat_inc(STAT_STATS_WAVE);
@@ -58,41 +58,24 @@ int vvhip_stats_device(const float* d_x, size_t n, size_t batch, size_t row_stri
     if (n >= ((size_t)1 << 32) || batch >= ((size_t)1 << 31)) return fail(ST_SIZE, "stats: n >= 2^32 or batch >= 2^31");
     if (device_count() <= 0) return fail(ST_UNSUP, "no HIP device");
     if (batch == 0) return ST_OK;
-    StatsSrc src;
-    src.x = d_x;
-    src.len = (long long)n;
-    src.rows = src.frames = (long long)batch;
-    src.row_stride = (long long)row_stride;
-    return stats_run(src, out, (hipStream_t)stream);
+    return stats_run(rows_src(d_x, n, batch, row_stride), out, (hipStream_t)stream);
 }
 
 int vvhip_stats_frames_device(const float* d_signal, size_t n, size_t nch, size_t ch_stride, size_t frame_len,
                               size_t hop, size_t frames, int center, const float* d_window, const vvhip_stats_out* o,
                               size_t out_ch_stride, void* stream) {
     if (!d_signal || !o) return ST_NULL;
-    if (hop == 0 || frame_len == 0) return ST_SIZE;
+    const FramesCall fc = {"stats_frames", n, nch, frame_len, hop, frames};
+    if (int st = fc.shape()) return st;
     const StatsOut out = stats_out(o, out_ch_stride);
     const unsigned mask = out.mask();
     if (mask == 0) return ST_OK;
     if (!stats_len_ok(mask, frame_len)) return ST_SIZE;
-    if (frame_len >= ((size_t)1 << 32) || n >= ((size_t)1 << 40) || nch >= ((size_t)1 << 31) ||
-        frames >= ((size_t)1 << 31) || nch * frames >= ((size_t)1 << 31))
-        return fail(ST_SIZE, "stats_frames: too many frames for one call");
-    if (device_count() <= 0) return fail(ST_UNSUP, "no HIP device");
-    if (frames == 0 || nch == 0) return ST_OK;
-    if (n == 0) return ST_SIZE;   // frames of an empty signal (center): nothing to reflect
-    StatsSrc src;
-    src.x = d_signal;
-    src.len = (long long)frame_len;
-    src.frames = (long long)frames;
-    src.rows = (long long)(nch * frames);
-    src.sig_n = (long long)n;
-    src.ch_stride = (long long)ch_stride;
-    src.hop = (long long)hop;
-    src.framed = 1;
-    src.center = center != 0;
-    src.win = d_window;
-    return stats_run(src, out, (hipStream_t)stream);
+    if (int st = fc.limits()) return st;
+    int st;
+    if (!fc.start(&st)) return st;
+    return stats_run(frames_src(d_signal, n, nch, ch_stride, frame_len, hop, frames, center, d_window), out,
+                     (hipStream_t)stream);
 }
 
 int vvhip_cross_correlation_device(const float* d_x, size_t nx, const float* d_y, size_t ny, size_t batch,

@@ -37,8 +37,7 @@
 //
 // Correlations: one workgroup per (row, lag); thread t adds the f64 products of
 // samples t, t + 256, ..., a butterfly per wave, the four waves in order.
-#include "framing_index.hpp"
-#include "vvhip_internal.hpp"
+#include "frame_src.hpp"
 
 #include <cmath>
 
@@ -66,34 +65,12 @@ struct StatsTotal {
     StatsMom m;
 };
 
-struct StatsRow {
-    const float* p;
-    long long start;
-    bool inside;      // every sample is p[start + i] (times the window)
-    long long at;     // where the row's values go in every output plane
-};
+using StatsRow = FrameRow<long long>;   // at: where the row's values go in every output plane
 
-// rows and frames are below 2^31: the (channel, frame) split is a 32-bit division
-__device__ __forceinline__ StatsRow stats_row(const StatsSrc& s, long long out_ch_stride, long long row) {
-    if (!s.framed) return {s.x + row * s.row_stride, 0, true, row};
-    const unsigned ch = (unsigned)row / (unsigned)s.frames, f = (unsigned)row - ch * (unsigned)s.frames;
-    const long long start = (long long)f * s.hop - (s.center ? s.len / 2 : 0);
-    return {s.x + ch * s.ch_stride, start, start >= 0 && start + s.len <= s.sig_n, ch * out_ch_stride + f};
-}
-
-// sample i of the row: k_fetch_frames' value (framing_kernels.hip) for a frame
-template <bool INSIDE>
-__device__ __forceinline__ float stats_sample(const StatsSrc& s, const StatsRow& r, long long i) {
-    float v;
-    if (INSIDE) {
-        v = r.p[r.start + i];
-    } else {
-        const long long k = r.start + i;
-        if (s.center) v = r.p[reflect_index(k, s.sig_n)];
-        else v = (k < 0 || k >= s.sig_n) ? 0.0f : r.p[k];
-    }
-    if (s.win) v = v * s.win[i];
-    return v;
+__device__ __forceinline__ StatsRow stats_row(const FrameSrc& s, long long out_ch_stride, long long row) {
+    return frame_row(
+        s, row, [&]() -> long long { return row; },
+        [&](unsigned ch, unsigned f) -> long long { return ch * out_ch_stride + f; });
 }
 
 __device__ __forceinline__ Ext ext_min(Ext a, Ext b) {
@@ -111,9 +88,9 @@ __device__ __forceinline__ bool crossing(float a, float b) { return (a > 0 && b 
 // sample c0 + j of the row, j < 4096: a row inside the signal is read through the
 // chunk's own pointers with a 32-bit offset
 template <bool INSIDE>
-__device__ __forceinline__ float chunk_sample(const StatsSrc& src, const StatsRow& rw, const float* xp,
+__device__ __forceinline__ float chunk_sample(const FrameSrc& src, const StatsRow& rw, const float* xp,
                                               const float* wp, long long c0, int j) {
-    if (!INSIDE) return stats_sample<false>(src, rw, c0 + j);
+    if (!INSIDE) return frame_sample<false>(src, rw, c0 + j);
     float v = xp[j];
     if (wp) v = v * wp[j];
     return v;
@@ -121,7 +98,7 @@ __device__ __forceinline__ float chunk_sample(const StatsSrc& src, const StatsRo
 
 // Pass 1 over samples [c0, c1) of a row by one wave; every lane returns the chunk's result.
 template <bool MOM, bool INSIDE>
-__device__ __forceinline__ StatsPart chunk_pass1(const StatsSrc& src, const StatsRow& rw, long long c0, long long c1,
+__device__ __forceinline__ StatsPart chunk_pass1(const FrameSrc& src, const StatsRow& rw, long long c0, long long c1,
                                                  float x0, int lane) {
 #pragma clang fp contract(off)
     double s1 = 0.0, s2 = 0.0;
@@ -132,7 +109,7 @@ __device__ __forceinline__ StatsPart chunk_pass1(const StatsSrc& src, const Stat
     const int len = (int)(c1 - c0);
     const unsigned i0 = (unsigned)c0;
     // the sample left of the chunk (lane 0's first neighbour); no pair ends at sample 0
-    float carry = c0 > 0 ? stats_sample<INSIDE>(src, rw, c0 - 1) : 0.0f;
+    float carry = c0 > 0 ? frame_sample<INSIDE>(src, rw, c0 - 1) : 0.0f;
     for (int j0 = 0; j0 < len; j0 += 64) {
         const int j = j0 + lane;
         const bool act = j < len;
@@ -162,7 +139,7 @@ __device__ __forceinline__ StatsPart chunk_pass1(const StatsSrc& src, const Stat
 }
 
 template <bool INSIDE>
-__device__ __forceinline__ StatsMom chunk_pass2(const StatsSrc& src, const StatsRow& rw, long long c0, long long c1,
+__device__ __forceinline__ StatsMom chunk_pass2(const FrameSrc& src, const StatsRow& rw, long long c0, long long c1,
                                                 double mean, int lane) {
 #pragma clang fp contract(off)
     double m2 = 0.0, m3 = 0.0, m4 = 0.0;
@@ -232,10 +209,10 @@ __device__ __forceinline__ void stats_store(const StatsPart& t, const StatsMom& 
 }
 
 template <bool MOM, bool INSIDE>
-__device__ __forceinline__ void stats_wave_row(const StatsSrc& src, const StatsRow& rw, bool central,
+__device__ __forceinline__ void stats_wave_row(const FrameSrc& src, const StatsRow& rw, bool central,
                                                const StatsOut& out, int lane) {
     const long long n = src.len;
-    const float x0 = stats_sample<INSIDE>(src, rw, 0);
+    const float x0 = frame_sample<INSIDE>(src, rw, 0);
     StatsPart tot = stats_zero(x0);
     for (long long c0 = 0; c0 < n; c0 += STATS_CHUNK) {
         const long long c1 = c0 + STATS_CHUNK < n ? c0 + STATS_CHUNK : n;
@@ -254,7 +231,7 @@ __device__ __forceinline__ void stats_wave_row(const StatsSrc& src, const StatsR
 
 // one wave per row, four rows per workgroup
 template <bool MOM>
-__global__ void __launch_bounds__(256) k_stats_wave(StatsSrc src, int central, StatsOut out) {
+__global__ void __launch_bounds__(256) k_stats_wave(FrameSrc src, int central, StatsOut out) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + wave;
@@ -266,7 +243,7 @@ __global__ void __launch_bounds__(256) k_stats_wave(StatsSrc src, int central, S
 
 // long route, pass 1: one wave per (row, chunk) -> parts[row * chunks + c]
 template <bool MOM>
-__global__ void __launch_bounds__(256) k_stats_part(StatsSrc src, long long chunks, StatsPart* __restrict__ parts) {
+__global__ void __launch_bounds__(256) k_stats_part(FrameSrc src, long long chunks, StatsPart* __restrict__ parts) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
     const long long item = (long long)blockIdx.x * 4 + wave;
@@ -275,14 +252,14 @@ __global__ void __launch_bounds__(256) k_stats_part(StatsSrc src, long long chun
     const long long c1 = c0 + STATS_CHUNK < src.len ? c0 + STATS_CHUNK : src.len;
     const StatsRow rw = stats_row(src, 0, row);
     StatsPart p;
-    if (rw.inside) p = chunk_pass1<MOM, true>(src, rw, c0, c1, stats_sample<true>(src, rw, 0), lane);
-    else p = chunk_pass1<MOM, false>(src, rw, c0, c1, stats_sample<false>(src, rw, 0), lane);
+    if (rw.inside) p = chunk_pass1<MOM, true>(src, rw, c0, c1, frame_sample<true>(src, rw, 0), lane);
+    else p = chunk_pass1<MOM, false>(src, rw, c0, c1, frame_sample<false>(src, rw, 0), lane);
     if (lane == 0) parts[item] = p;
 }
 
 // one thread per row: the chunks' pass-1 results in chunk order -> totals[row].p;
 // last != 0: nothing about the mean is wanted, the outputs are written here
-__global__ void __launch_bounds__(64) k_stats_combine(StatsSrc src, long long chunks,
+__global__ void __launch_bounds__(64) k_stats_combine(FrameSrc src, long long chunks,
                                                       const StatsPart* __restrict__ parts,
                                                       StatsTotal* __restrict__ totals, int last, StatsOut out) {
     const long long row = (long long)blockIdx.x * 64 + threadIdx.x;
@@ -301,7 +278,7 @@ __global__ void __launch_bounds__(64) k_stats_combine(StatsSrc src, long long ch
 }
 
 // long route, pass 2: one wave per (row, chunk) -> moms[row * chunks + c]
-__global__ void __launch_bounds__(256) k_stats_mom(StatsSrc src, long long chunks,
+__global__ void __launch_bounds__(256) k_stats_mom(FrameSrc src, long long chunks,
                                                    const StatsTotal* __restrict__ totals,
                                                    StatsMom* __restrict__ moms) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -318,7 +295,7 @@ __global__ void __launch_bounds__(256) k_stats_mom(StatsSrc src, long long chunk
     if (lane == 0) moms[item] = m;
 }
 
-__global__ void __launch_bounds__(64) k_stats_finish(StatsSrc src, long long chunks,
+__global__ void __launch_bounds__(64) k_stats_finish(FrameSrc src, long long chunks,
                                                      const StatsTotal* __restrict__ totals,
                                                      const StatsMom* __restrict__ moms, StatsOut out) {
     const long long row = (long long)blockIdx.x * 64 + threadIdx.x;
@@ -351,7 +328,7 @@ __global__ void __launch_bounds__(256) k_xcorr(const float* __restrict__ x, long
     r[item] = count == 0 ? 0.0f : (float)(sum / (double)(biased ? nx : count));
 }
 
-bool stats_src_ok(const StatsSrc& src) {
+bool stats_src_ok(const FrameSrc& src) {
     return src.len > 0 && src.len < (1LL << 32) && src.rows < (1LL << 31) && src.frames > 0;
 }
 
@@ -360,7 +337,7 @@ bool stats_src_ok(const StatsSrc& src) {
 size_t stats_part_bytes() { return sizeof(StatsPart) + sizeof(StatsMom); }
 size_t stats_total_bytes() { return sizeof(StatsTotal); }
 
-hipError_t launch_stats_wave(const StatsSrc& src, const StatsOut& out, hipStream_t s) {
+hipError_t launch_stats_wave(const FrameSrc& src, const StatsOut& out, hipStream_t s) {
     const unsigned mask = out.mask();
     if (src.rows <= 0 || mask == 0) return hipSuccess;
     if (!stats_src_ok(src)) return hipErrorInvalidValue;
@@ -371,7 +348,7 @@ hipError_t launch_stats_wave(const StatsSrc& src, const StatsOut& out, hipStream
     return hipGetLastError();
 }
 
-hipError_t launch_stats_long(const StatsSrc& src, const StatsOut& out, void* parts, void* totals, hipStream_t s) {
+hipError_t launch_stats_long(const FrameSrc& src, const StatsOut& out, void* parts, void* totals, hipStream_t s) {
     const unsigned mask = out.mask();
     if (src.rows <= 0 || mask == 0) return hipSuccess;
     if (!stats_src_ok(src)) return hipErrorInvalidValue;

@@ -90,6 +90,23 @@ hipError_t launch_fetch_frames(const float* sig, long long base, long long n, fl
                                hipStream_t s);
 hipError_t launch_overlap_add(const float* frames, long long count, float* out, long long out_len, long long len,
                               long long hop, long long frame0, hipStream_t s);
+// The rows a per-frame launch (LPC, statistics, pitch) reads, `rows` rows of
+// len samples, of one of two kinds:
+//   framed 0: row r is x + r * row_stride (frames = rows);
+//   framed 1: row ch * frames + f is frame f of channel x + ch * ch_stride, an
+//     n = sig_n sample signal, with exactly the value launch_fetch_frames gives
+//     its sample i: sample f * hop - (center ? len / 2 : 0) + i of the signal,
+//     zero outside it or, when center, reflected into it (framing.c:21-56), times
+//     win[i] in one rounded multiply when win is not null.
+// rows and frames are below 2^31.  frame_src.hpp is the device side: the one
+// statement of that value, which the frame gather itself reads through.
+struct FrameSrc {
+    const float* x = nullptr;
+    long long len = 0, rows = 0, frames = 0, row_stride = 0;
+    long long sig_n = 0, ch_stride = 0, hop = 0;
+    int framed = 0, center = 0;
+    const float* win = nullptr;
+};
 
 // Persistent-grid sizing: resident blocks for `kernel` x CUs, capped by work.
 // CUs x resident workgroups of `kernel` (capped at max_per_cu when > 0), at most work_blocks
@@ -282,17 +299,7 @@ constexpr int INTERP_SHARED_ROWS = 8;
 hipError_t launch_interp(const InterpArgs& a, int method, int rows, hipStream_t s);
 
 // ---- LPC (lpc_kernels.hip), src/envelope/lpc.c ------------------------------
-// The rows an LPC launch reads: `rows` contiguous rows of len samples
-// (framed 0, frames = rows), or the frames of nch = rows / frames channels
-// gathered as k_fetch_frames gathers them (framed 1: zero padding, reflection
-// when center, times win when not null).
-struct LpcSrc {
-    const float* x = nullptr;
-    long long len = 0, rows = 0, frames = 0;
-    long long sig_n = 0, ch_stride = 0, hop = 0;
-    int framed = 0, center = 0;
-    const float* win = nullptr;
-};
+// The rows are described by a FrameSrc (above; rows of a batch have row_stride = len).
 // Where the coefficient rows go: row (ch, f) = (row / frames, row % frames) at
 // a + ch * a_ch_stride + f * (order + 1) and err + ch * err_ch_stride + f.
 // flag (may be null): set to 1 when a row had r[0] <= 0.
@@ -309,9 +316,9 @@ inline bool lpc_wave_supported(long long len, long long order) {
 }
 // wave kernel: autocorrelation rows into r [rows][order + 1] (r not null), or
 // autocorrelation + Levinson into out; lpc_wave_supported shapes only
-hipError_t launch_lpc_wave(const LpcSrc& src, int order, float* r, const LpcOut& out, hipStream_t s);
+hipError_t launch_lpc_wave(const FrameSrc& src, int order, float* r, const LpcOut& out, hipStream_t s);
 // any order < len: one workgroup per row, r [rows][order + 1]
-hipError_t launch_autocorr_generic(const LpcSrc& src, long long order, float* r, hipStream_t s);
+hipError_t launch_autocorr_generic(const FrameSrc& src, long long order, float* r, hipStream_t s);
 // r [rows][order + 1] -> out, the reference's recursion per row (lpc.c:24-38);
 // generic 0 needs order <= LPC_WAVE_ORDER
 hipError_t launch_levinson(const float* r, long long order, long long rows, int generic, const LpcOut& out,
@@ -322,16 +329,7 @@ hipError_t launch_lpspec(const float* a, long long order, const float* gain, flo
                          long long batch, int plus, float* mag, hipStream_t s);
 
 // ---- array statistics (stats_kernels.hip), src/core/core.c:42-108, stats.c:10-139 ----
-// The rows a statistics launch reads: `rows` rows of len samples row_stride
-// floats apart (framed 0), or the frames of nch = rows / frames channels
-// gathered as k_fetch_frames gathers them (framed 1).
-struct StatsSrc {
-    const float* x = nullptr;
-    long long len = 0, rows = 0, frames = 0, row_stride = 0;
-    long long sig_n = 0, ch_stride = 0, hop = 0;
-    int framed = 0, center = 0;
-    const float* win = nullptr;
-};
+// The rows are described by a FrameSrc (above).
 // the outputs, in the order of vv_dsp_stats_out's members; bit k of a mask = output k
 enum StatsBit : int {
     STATS_SUM, STATS_MEAN, STATS_VAR, STATS_RMS, STATS_MIN, STATS_MAX, STATS_CREST, STATS_SKEW, STATS_KURT,
@@ -360,11 +358,11 @@ constexpr long long STATS_WAVE_LEN = 16384;    // rows up to here: one wave walk
 size_t stats_part_bytes();
 size_t stats_total_bytes();
 // one wave per row (any len < 2^32; the shim sends len <= STATS_WAVE_LEN)
-hipError_t launch_stats_wave(const StatsSrc& src, const StatsOut& out, hipStream_t s);
+hipError_t launch_stats_wave(const FrameSrc& src, const StatsOut& out, hipStream_t s);
 // one wave per (row, chunk), then the chunks' partial results combined per row in
 // chunk order: the same sums in the same order as the wave kernel's.
 // parts: rows * chunks * stats_part_bytes(), totals: rows * stats_total_bytes()
-hipError_t launch_stats_long(const StatsSrc& src, const StatsOut& out, void* parts, void* totals, hipStream_t s);
+hipError_t launch_stats_long(const FrameSrc& src, const StatsOut& out, void* parts, void* totals, hipStream_t s);
 // r [rows][r_len]: r[lag] = sum_i x[i] y[i + lag] in f64 over the `count` overlapping
 // samples, over count (biased 0) or over nx (biased 1); 0 where count == 0.
 // Rows of x / y are nx / ny floats apart.
@@ -372,7 +370,7 @@ hipError_t launch_xcorr(const float* x, long long nx, const float* y, long long 
                         int biased, float* r, hipStream_t s);
 
 // ---- per-frame pitch by YIN (pitch_kernels.hip), include/vv_dsp/features/pitch.h ----
-// The rows are described by a StatsSrc (rows, or the frames of a signal).
+// The rows are described by a FrameSrc (above).
 constexpr long long PITCH_MAX_FRAME = 16384;     // samples of a row
 constexpr int PITCH_MAX_LAG = 8191;              // tau_max
 constexpr size_t PITCH_LDS_MAX = 128u << 10;     // the longest row as f32 and its lags as f64
@@ -396,7 +394,7 @@ struct PitchOut {
 // one wave per row, one launch; nothing wanted or no rows: nothing launched.
 // The row sits in LDS as f64 where four rows fit 64 KiB, as f32 beyond or with
 // f32_rows (knob PITCH_F32 = 1): the conversion is exact, the bits are the same.
-hipError_t launch_pitch(const StatsSrc& src, const PitchCfg& cfg, const PitchOut& out, bool f32_rows, hipStream_t s);
+hipError_t launch_pitch(const FrameSrc& src, const PitchCfg& cfg, const PitchOut& out, bool f32_rows, hipStream_t s);
 
 // ---- biquad cascade (iir_kernels.hip), src/filter/iir.c:21-43 -----------------
 constexpr int IIR_MAX_STAGES = 8;        // stages one walk holds in registers; longer cascades run in groups

@@ -704,19 +704,36 @@ def num_frames(n, frame_len, hop, center=False):
     return lib().vv_dsp_get_num_frames(n, frame_len, hop, int(bool(center)))
 
 
+def _signal(sig, who):
+    """(sig2, nch, n) of the signal of a per-frame call: float32 device rows (nch, n) or (n,)"""
+    sig2 = sig if sig.dim() == 2 else sig.unsqueeze(0)
+    if sig.dim() not in (1, 2) or sig2.dtype != torch.float32 or sig2.stride(1) != 1 or not sig2.is_cuda:
+        raise VvError(f"{who} signal: float32 device rows with unit sample stride")
+    return (sig2,) + tuple(sig2.shape)
+
+
+def _window(window, frame_len, who):
+    """the optional window of a per-frame call as a pointer argument"""
+    if window is None:
+        return None
+    _expect(window, torch.float32, frame_len, f"{who} window")
+    return _ptr(window)
+
+
+def _planes_of(planes, x):
+    """the result planes of a (batch, n) input, or their first rows for a (n,) input"""
+    return planes if x.dim() == 2 else {k: v[0] for k, v in planes.items()}
+
+
 def lpc_frames(sig, frame_len, hop, order, window=None, center=False, out=None, stream=None):
     """Signal (nch, n) or (n,) float32 -> a (nch, frames, order + 1), err (nch, frames):
     the frames of vv_dsp_fetch_frames_device (times `window`, frame_len float32, when
     given) through lpc() in one kernel, bit-identical to the two steps.  out: (a, err)
     tensors to write into."""
-    sig2 = sig if sig.dim() == 2 else sig.unsqueeze(0)
-    if sig.dim() not in (1, 2) or sig2.dtype != torch.float32 or sig2.stride(1) != 1 or not sig2.is_cuda:
-        raise VvError("lpc_frames signal: float32 device rows with unit sample stride")
+    sig2, nch, n = _signal(sig, "lpc_frames")
     if frame_len <= 0 or hop <= 0 or order + 1 > frame_len:
         raise VvError(f"lpc_frames: frame_len {frame_len}, hop {hop}, order {order}")
-    nch, n = sig2.shape
-    if window is not None:
-        _expect(window, torch.float32, frame_len, "lpc_frames window")
+    win = _window(window, frame_len, "lpc_frames")
     fr = num_frames(n, frame_len, hop, center)
     if out is None:
         a = torch.empty((nch, fr, order + 1), dtype=torch.float32, device=sig.device)
@@ -727,7 +744,7 @@ def lpc_frames(sig, frame_len, hop, order, window=None, center=False, out=None, 
     _expect(err, torch.float32, nch * fr, "lpc_frames error")
     # rows may be sig2.stride(0) >= n floats apart (a view of a wider buffer)
     _check(lib().vv_dsp_lpc_frames_device(_vp(sig2.data_ptr()), n, nch, sig2.stride(0), frame_len, hop,
-                                          int(bool(center)), None if window is None else _ptr(window), order,
+                                          int(bool(center)), win, order,
                                           _ptr(a), fr * (order + 1), _ptr(err), fr, _stream(stream)),
            "lpc_frames_device")
     return (a, err) if sig.dim() == 2 or out is not None else (a[0], err[0])
@@ -778,7 +795,7 @@ def stats(x, what, stream=None):
     if planes and b:
         _check(lib().vv_dsp_stats_device(_vp(x2.data_ptr()), n, b, x2.stride(0) if b > 1 else n, C.byref(out),
                                          _stream(stream)), "stats_device")
-    return planes if x.dim() == 2 else {k: v[0] for k, v in planes.items()}
+    return _planes_of(planes, x)
 
 
 def stats_frames(sig, frame_len, hop, what, window=None, center=False, stream=None):
@@ -786,21 +803,17 @@ def stats_frames(sig, frame_len, hop, what, window=None, center=False, stream=No
     {name: (nch, frames) or (frames,)}, the frames of vv_dsp_fetch_frames_device (times
     `window`, frame_len float32, when given) through stats() in one kernel, bit-identical
     to the two steps."""
-    sig2 = sig if sig.dim() == 2 else sig.unsqueeze(0)
-    if sig.dim() not in (1, 2) or sig2.dtype != torch.float32 or sig2.stride(1) != 1 or not sig2.is_cuda:
-        raise VvError("stats_frames signal: float32 device rows with unit sample stride")
+    sig2, nch, n = _signal(sig, "stats_frames")
     if frame_len <= 0 or hop <= 0:
         raise VvError(f"stats_frames: frame_len {frame_len}, hop {hop}")
-    nch, n = sig2.shape
-    if window is not None:
-        _expect(window, torch.float32, frame_len, "stats_frames window")
+    win = _window(window, frame_len, "stats_frames")
     fr = num_frames(n, frame_len, hop, center)
     planes, out = _stats_planes(what, frame_len, (nch, fr), sig.device, "stats_frames")
     if planes and fr and nch:
         _check(lib().vv_dsp_stats_frames_device(_vp(sig2.data_ptr()), n, nch, sig2.stride(0), frame_len, hop,
-                                                int(bool(center)), None if window is None else _ptr(window),
+                                                int(bool(center)), win,
                                                 C.byref(out), fr, _stream(stream)), "stats_frames_device")
-    return planes if sig.dim() == 2 else {k: v[0] for k, v in planes.items()}
+    return _planes_of(planes, sig)
 
 
 def pitch_lag_range(params, frame_len):
@@ -841,7 +854,7 @@ def pitch(x, params, what, stream=None):
     if planes and b:
         _check(lib().vv_dsp_pitch_device(_vp(x2.data_ptr()), n, b, x2.stride(0) if b > 1 else n, C.byref(params),
                                          C.byref(out), tau_max + 1, _stream(stream)), "pitch_device")
-    return planes if x.dim() == 2 else {k: v[0] for k, v in planes.items()}
+    return _planes_of(planes, x)
 
 
 def pitch_frames(sig, frame_len, hop, params, what, window=None, center=False, stream=None):
@@ -849,23 +862,19 @@ def pitch_frames(sig, frame_len, hop, params, what, window=None, center=False, s
     {name: (nch, frames[, tau_max + 1]) or (frames[, tau_max + 1])}, the frames of
     vv_dsp_fetch_frames_device (times `window`, frame_len float32, when given) through
     pitch() in one kernel, bit-identical to the two steps."""
-    sig2 = sig if sig.dim() == 2 else sig.unsqueeze(0)
-    if sig.dim() not in (1, 2) or sig2.dtype != torch.float32 or sig2.stride(1) != 1 or not sig2.is_cuda:
-        raise VvError("pitch_frames signal: float32 device rows with unit sample stride")
+    sig2, nch, n = _signal(sig, "pitch_frames")
     if frame_len <= 0 or hop <= 0:
         raise VvError(f"pitch_frames: frame_len {frame_len}, hop {hop}")
-    nch, n = sig2.shape
-    if window is not None:
-        _expect(window, torch.float32, frame_len, "pitch_frames window")
+    win = _window(window, frame_len, "pitch_frames")
     _, tau_max, _ = pitch_lag_range(params, frame_len)
     fr = num_frames(n, frame_len, hop, center)
     planes, out = _pitch_planes(what, tau_max, (nch, fr), sig.device, "pitch_frames")
     if planes and fr and nch:
         _check(lib().vv_dsp_pitch_frames_device(_vp(sig2.data_ptr()), n, nch, sig2.stride(0), frame_len, hop,
-                                                int(bool(center)), None if window is None else _ptr(window),
+                                                int(bool(center)), win,
                                                 C.byref(params), C.byref(out), fr, fr * (tau_max + 1),
                                                 _stream(stream)), "pitch_frames_device")
-    return planes if sig.dim() == 2 else {k: v[0] for k, v in planes.items()}
+    return _planes_of(planes, sig)
 
 
 def autocorrelation(x, r_len, biased=False, stream=None):
