@@ -77,12 +77,12 @@ def frames_of(n, nfft=1024, hop=256):
     return 1 if n < nfft else 1 + (n - nfft + hop) // hop
 
 
-def case_fir(L, s, nch=8, n=1 << 24):
+def case_fir(L, s, nch=8, n=1 << 24, taps=257):
     x, y = buf(("fir", nch, n), lambda: (torch.rand(nch, n, device="cuda") * 2 - 1, torch.empty(nch, n, device="cuda")))
-    h = np.zeros(257, np.float32)
-    ok(L, L.vv_dsp_fir_design_lowpass(h.ctypes.data, 257, 0.25, 2), "design")
+    h = np.zeros(taps, np.float32)
+    ok(L, L.vv_dsp_fir_design_lowpass(h.ctypes.data, taps, 0.25, 2), "design")
     p = vp()
-    ok(L, L.vv_dsp_fir_plan_create(h.ctypes.data, 257, C.byref(p)), "fir plan")
+    ok(L, L.vv_dsp_fir_plan_create(h.ctypes.data, taps, C.byref(p)), "fir plan")
     return (lambda: ok(L, L.vv_dsp_fir_apply_fft_device(p, x.data_ptr(), y.data_ptr(), n, nch, n, n, s), "fir")), \
         2 * nch * n * 4, (lambda: y.clone())
 
@@ -159,14 +159,28 @@ def case_mel(L, s, mfcc, nch=32, seconds=600):
         nch * n * 4 + nch * fr * w * 4, (lambda: out.clone())
 
 
-def case_c2c(L, s, n=1024, batch=65536):
+def case_c2c(L, s, n=1024, batch=65536, fwd=1):
     x, y = buf(("c2c", n, batch), lambda: (torch.complex(torch.rand(batch, n, device="cuda") - 0.5,
                                                          torch.rand(batch, n, device="cuda") - 0.5),
                                            torch.empty(batch, n, dtype=torch.complex64, device="cuda")))
     p = vp()
-    ok(L, L.vv_dsp_fft_make_plan_many(n, 0, 1, batch, C.byref(p)), "fft plan")
+    ok(L, L.vv_dsp_fft_make_plan_many(n, 0, fwd, batch, C.byref(p)), "fft plan")
     return (lambda: ok(L, L.vv_dsp_fft_execute_device(p, x.data_ptr(), y.data_ptr(), s), "fft")), \
         2 * batch * n * 8, (lambda: y.clone())
+
+
+def case_czt(L, s, n, m, batch):
+    """batched chirp-z rows cpx[batch][n] -> cpx[batch][m] (above P = 4096: the element-wise chain)"""
+    x, y = buf(("czt", n, m, batch), lambda: (torch.complex(torch.rand(batch, n, device="cuda") - 0.5,
+                                                            torch.rand(batch, n, device="cuda") - 0.5),
+                                              torch.empty(batch, m, dtype=torch.complex64, device="cuda")))
+    L.vv_dsp_czt_plan_create.argtypes = [sz, sz, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(vp)]
+    L.vv_dsp_czt_execute_device.argtypes = [vp, vp, C.c_int, sz, vp, vp]
+    w = np.exp(-2j * np.pi * 0.13 / m)
+    p = vp()
+    ok(L, L.vv_dsp_czt_plan_create(n, m, w.real, w.imag, 1.0, 0.0, C.byref(p)), "czt plan")
+    return (lambda: ok(L, L.vv_dsp_czt_execute_device(p, x.data_ptr(), 0, batch, y.data_ptr(), s), "czt")), \
+        batch * (n + m) * 8, (lambda: y.clone())
 
 
 def case_real(L, s, n, batch, kind):
@@ -268,6 +282,12 @@ def burst(case, k):
 
 CASES = {
     "fir": case_fir,
+    # the long-transform routes: two-pass four-step both ways, Bluestein, the chirp-z chain at P = 8192, long FIR
+    **{f"c2c2p{lg}{d}": (lambda L, s, lg=lg, b=b, f=f: case_c2c(L, s, 1 << lg, b, f))
+       for lg, b in ((16, 64), (20, 4)) for d, f in (("", 1), ("inv", -1))},
+    "blue48000": lambda L, s: case_c2c(L, s, 48000, 8),
+    "czt8192": lambda L, s: case_czt(L, s, 3000, 1200, 2048),
+    "firlong": lambda L, s: case_fir(L, s, nch=8, n=1 << 22, taps=6200),
     "stft": lambda L, s: case_stft_rows(L, s, "mag", 32, 600),
     "stft60": lambda L, s: case_stft_rows(L, s, "mag", 1, 60),
     "stft256ch": lambda L, s: case_stft_rows(L, s, "mag", 256, 600),

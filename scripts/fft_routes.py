@@ -31,8 +31,8 @@ def cpx(batch, n, offset=0):
     return torch.view_as_complex(signal(1, 2 * (offset + batch * n)).view(-1, 2))[offset:].view(batch, n)
 
 
-def show(tag, n, kind, note, knobs):
-    print("%-10s n %6d %-8s rows %d%s%s" % (tag, n, kind, BATCH, note, "".join(" %s=%d" % kv for kv in knobs.items())),
+def show(tag, n, kind, note, knobs, batch=BATCH):
+    print("%-10s n %6d %-8s rows %d%s%s" % (tag, n, kind, batch, note, "".join(" %s=%d" % kv for kv in knobs.items())),
           flush=True)
 
 
@@ -41,18 +41,18 @@ def done(y):
     print("    out %s bits %d" % (tuple(y.shape), bits(y)), flush=True)
 
 
-def run_fft(tag, n, kind, unaligned=False, **knobs):
+def run_fft(tag, n, kind, unaligned=False, batch=BATCH, **knobs):
     """kind c2c / c2c-inv / r2c / c2r; unaligned: the input 8 B past a 16 B boundary"""
     if kind == "r2c":
-        x = signal(BATCH, n, offset=2 if unaligned else 0)
-        plan = vv.FftPlan(n, vv.R2C, vv.FWD, batch=BATCH)
+        x = signal(batch, n, offset=2 if unaligned else 0)
+        plan = vv.FftPlan(n, vv.R2C, vv.FWD, batch=batch)
     elif kind == "c2r":
-        x = cpx(BATCH, n // 2 + 1, offset=1 if unaligned else 0)
-        plan = vv.FftPlan(n, vv.C2R, vv.BWD, batch=BATCH)
+        x = cpx(batch, n // 2 + 1, offset=1 if unaligned else 0)
+        plan = vv.FftPlan(n, vv.C2R, vv.BWD, batch=batch)
     else:
-        x = cpx(BATCH, n, offset=1 if unaligned else 0)
-        plan = vv.FftPlan(n, vv.C2C, vv.BWD if kind == "c2c-inv" else vv.FWD, batch=BATCH)
-    show(tag, n, kind, " in 8 B past 16 B" if unaligned else "", knobs)
+        x = cpx(batch, n, offset=1 if unaligned else 0)
+        plan = vv.FftPlan(n, vv.C2C, vv.BWD if kind == "c2c-inv" else vv.FWD, batch=batch)
+    show(tag, n, kind, " in 8 B past 16 B" if unaligned else "", knobs, batch)
     with vv.knobs(**knobs):
         done(plan(x))
 

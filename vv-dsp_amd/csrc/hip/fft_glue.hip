@@ -177,6 +177,16 @@ hipError_t launch_take_real(const float2* in, float* out, long long count, hipSt
     return hipGetLastError();
 }
 
+__global__ void k_promote_real(const float* __restrict__ in, float2* __restrict__ out, long long count) {
+    VVH_GRID_STRIDE(i, count) out[i] = make_float2(in[i], 0.0f);
+}
+
+hipError_t launch_promote_real(const float* in, float2* out, long long count, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_promote_real, dim3(stride_blocks(count)), dim3(256), 0, s, in, out, count);
+    return hipGetLastError();
+}
+
 __global__ void k_zero_nyq(float2* out, long long n, long long batch, long long dist) {
     const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (f < batch) out[f * dist + n / 2].y = 0.0f;

@@ -1,5 +1,5 @@
-// fir_long.hip -- the glue kernels of overlap-save for filters longer than the
-// fused kernels take (shim_fir.hip fir_ols_long).
+// fir_long.hip -- the gather and scatter kernels of overlap-save for filters
+// longer than the fused kernels take (shim_fir.hip fir_ols_long).
 #include "fir_common.hpp"
 #include "vvhip_internal.hpp"
 
@@ -10,14 +10,14 @@ namespace vvh {
 // blocks j (2 per complex row: z = a + i b, as k_fir_pair) gathered into rows
 // of an N-point batch, FFT, x H (FFT(h) unscaled; the inverse applies 1/N),
 // inverse FFT, and the block outputs LE..N-1 scattered back.  The FFTs are the
-// four-step kernels (large_fft.hip); these three kernels are the glue.
+// four-step kernels (fourstep_fft.hip) and the product is k_cmul_rows
+// (chirp_glue.hip); these two kernels are the rest of the glue.
 // Row q of a chunk is pair p = p0 + q over (channel, pair) items.
 // ------------------------------------------------------------------------
 __global__ void k_fir_long_gather(const float* x, long long n, long long x_stride, long long nfft, long long le,
                                   long long lout, long long ppc, long long p0, long long rows, float2* z) {
     const long long total = rows * nfft;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
+    VVH_GRID_STRIDE(i, total) {
         const long long q = i / nfft, e = i - q * nfft, p = p0 + q;
         const long long c = p / ppc, j = 2 * (p - c * ppc);
         const float* xc = x + c * x_stride;
@@ -28,17 +28,10 @@ __global__ void k_fir_long_gather(const float* x, long long n, long long x_strid
     }
 }
 
-__global__ void k_fir_long_mul(float2* Z, const float2* H, long long nfft, long long total) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x)
-        Z[i] = cmul(Z[i], H[i % nfft]);
-}
-
 __global__ void k_fir_long_scatter(const float2* z, float* y, long long n, long long y_stride, long long nfft,
                                    long long le, long long lout, long long ppc, long long p0, long long rows) {
     const long long total = rows * lout;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
+    VVH_GRID_STRIDE(i, total) {
         const long long q = i / lout, k = i - q * lout, p = p0 + q;
         const long long c = p / ppc, j = 2 * (p - c * ppc);
         const float2 v = z[q * nfft + le + k];
@@ -49,23 +42,12 @@ __global__ void k_fir_long_scatter(const float2* z, float* y, long long n, long 
     }
 }
 
-static unsigned glue_grid(long long total) {
-    long long b = (total + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
-
 hipError_t launch_fir_long_gather(const float* x, long long n, long long x_stride, long long nfft, long long le,
                                   long long lout, long long ppc, long long p0, long long rows, float2* z,
                                   hipStream_t s) {
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fir_long_gather, dim3(glue_grid(rows * nfft)), dim3(256), 0, s, x, n, x_stride, nfft, le,
+    hipLaunchKernelGGL(k_fir_long_gather, dim3(stride_blocks(rows * nfft)), dim3(256), 0, s, x, n, x_stride, nfft, le,
                        lout, ppc, p0, rows, z);
-    return hipGetLastError();
-}
-
-hipError_t launch_fir_long_mul(float2* Z, const float2* H, long long nfft, long long rows, hipStream_t s) {
-    if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fir_long_mul, dim3(glue_grid(rows * nfft)), dim3(256), 0, s, Z, H, nfft, rows * nfft);
     return hipGetLastError();
 }
 
@@ -73,7 +55,7 @@ hipError_t launch_fir_long_scatter(const float2* z, float* y, long long n, long 
                                    long long le, long long lout, long long ppc, long long p0, long long rows,
                                    hipStream_t s) {
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fir_long_scatter, dim3(glue_grid(rows * lout)), dim3(256), 0, s, z, y, n, y_stride, nfft,
+    hipLaunchKernelGGL(k_fir_long_scatter, dim3(stride_blocks(rows * lout)), dim3(256), 0, s, z, y, n, y_stride, nfft,
                        le, lout, ppc, p0, rows);
     return hipGetLastError();
 }

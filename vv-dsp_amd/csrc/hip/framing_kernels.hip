@@ -25,8 +25,7 @@ __global__ void __launch_bounds__(256) k_fetch_frames(const float* __restrict__ 
     src.center = center;
     src.win = win;
     const long long total = count * len;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
-         e += (long long)gridDim.x * blockDim.x) {
+    VVH_GRID_STRIDE(e, total) {
         const long long f = e / len, i = e - f * len;
         const long long start = (frame0 + f) * hop - (center ? len / 2 : 0);
         __builtin_nontemporal_store(frame_sample<false>(src, sig, start, i, base), out + e);
@@ -59,9 +58,7 @@ hipError_t launch_fetch_frames(const float* sig, long long base, long long n, fl
                                hipStream_t s) {
     const long long total = count * len;
     if (total <= 0) return hipSuccess;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_fetch_frames, dim3((unsigned)blocks), dim3(256), 0, s, sig, base, n, out, len, hop, frame0,
+    hipLaunchKernelGGL(k_fetch_frames, dim3(stride_blocks(total)), dim3(256), 0, s, sig, base, n, out, len, hop, frame0,
                        count, center, win);
     return hipGetLastError();
 }
@@ -73,10 +70,8 @@ hipError_t launch_overlap_add(const float* frames, long long count, float* out, 
     long long j1 = (frame0 + count - 1) * hop + len;
     if (j1 > out_len) j1 = out_len;
     if (j0 >= j1) return hipSuccess;
-    long long blocks = (j1 - j0 + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_overlap_add, dim3((unsigned)blocks), dim3(256), 0, s, frames, count, out, out_len, len, hop,
-                       frame0, j0, j1);
+    hipLaunchKernelGGL(k_overlap_add, dim3(stride_blocks(j1 - j0)), dim3(256), 0, s, frames, count, out, out_len, len,
+                       hop, frame0, j0, j1);
     return hipGetLastError();
 }
 

@@ -10,8 +10,7 @@ namespace vvh {
 // frame order, so the f32 rounding matches sequential accumulation.
 __global__ void k_ola(long long nfft, long long hop, const float2* tf, long long count,
                       const float* win, float* out_add, float* norm_add, long long len) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < len;
-         i += (long long)gridDim.x * blockDim.x) {
+    VVH_GRID_STRIDE(i, len) {
         long long f_hi = i / hop;
         if (f_hi > count - 1) f_hi = count - 1;
         long long f_lo = (i - nfft + 1 + hop - 1) / hop;
@@ -223,9 +222,7 @@ hipError_t launch_ola(long long nfft, long long hop, const float2* time_frames, 
                       const float* win, float* out_add, float* norm_add, hipStream_t s) {
     const long long len = (count - 1) * hop + nfft;
     if (count <= 0) return hipSuccess;
-    long long blocks = (len + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_ola, dim3((unsigned)blocks), dim3(256), 0, s, nfft, hop, time_frames, count, win,
+    hipLaunchKernelGGL(k_ola, dim3(stride_blocks(len)), dim3(256), 0, s, nfft, hop, time_frames, count, win,
                        out_add, norm_add, len);
     return hipGetLastError();
 }

@@ -113,8 +113,7 @@ __global__ void __launch_bounds__(PH_T) k_phase_out(const In* z, long long n, lo
 }
 
 __global__ void k_inst_freq(const float* p, long long n, long long total, double scale, float* f) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
+    VVH_GRID_STRIDE(i, total) {
         const long long k = i % n;
         if (k == 0) {
             f[i] = 0.0f;
@@ -153,9 +152,7 @@ hipError_t launch_inst_freq(const float* phase, long long n, long long batch, do
                             hipStream_t s) {
     const long long total = n * batch;
     if (total <= 0) return hipSuccess;
-    long long b = (total + 255) / 256;
-    if (b > 65536) b = 65536;
-    hipLaunchKernelGGL(k_inst_freq, dim3((unsigned)b), dim3(256), 0, s, phase, n, total, scale, freq);
+    hipLaunchKernelGGL(k_inst_freq, dim3(stride_blocks(total)), dim3(256), 0, s, phase, n, total, scale, freq);
     return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // pow2_launch.hpp -- what the launchers of the power-of-two register/LDS kernels
-// (fft_c2c.hip, fft_r2c.hip, fft_c2r.hip, hilbert_fused.hip, dct2_fused.hip,
-// czt_kernels.hip) share.  Host code only; private to these units.
+// (fft_c2c.hip, fft_real.hip, analytic_kernels.hip, czt_kernels.hip) and of the
+// two-pass four-step (fourstep_fft.hip) share.  Host code only; private to these units.
 #pragma once
 #include "vvhip_internal.hpp"
 

@@ -113,7 +113,7 @@ static int fir_ols_long(vvhip_fir* f, size_t nr, const float* d_x, float* d_y, s
         HIPCHK(launch_fir_long_gather(d_x, (long long)n, (long long)x_stride, N, le, lout, ppc, p0, r, A, s),
                ST_INTERNAL);
         HIPCHK(launch_c2c_large(N, 1, A, B, r, s), ST_INTERNAL);
-        HIPCHK(launch_fir_long_mul(B, H, N, r, s), ST_INTERNAL);
+        HIPCHK(launch_cmul_rows(B, H, N, r, s), ST_INTERNAL);
         HIPCHK(launch_c2c_large(N, 0, B, A, r, s), ST_INTERNAL);
         HIPCHK(launch_fir_long_scatter(A, d_y, (long long)n, (long long)y_stride, N, le, lout, ppc, p0, r, s),
                ST_INTERNAL);

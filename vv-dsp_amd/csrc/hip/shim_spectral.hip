@@ -1,7 +1,8 @@
 // shim_spectral.hip -- the chirp-z transform (src/spectral/czt.c:58-178) and
 // the cepstrum family (src/envelope/cepstrum.c:7-78, minphase.c:7-31):
-// element-wise kernels of czt_kernels.hip around the library's own FFTs
-// (fft_run); and the spectral utilities (src/spectral/utils.c:5-73, below).
+// the one-pass kernels of czt_kernels.hip, or the element-wise kernels of
+// chirp_glue.hip and ceps_stages.hip around the library's own FFTs (fft_run);
+// and the spectral utilities (src/spectral/utils.c:5-73, below).
 #include "shim_common.hpp"
 
 #include <cmath>
@@ -52,15 +53,15 @@ int czt_run(const vvhip_czt* h, const void* x, int real_in, size_t batch, float2
     float2* ap = (float2*)a.p;
     for (size_t r0 = 0; r0 < batch; r0 += rows) {
         const size_t rc = batch - r0 < rows ? batch - r0 : rows;
-        HIPCHK(launch_czt_pre((const char*)x + esz * h->n * r0, real_in, (long long)h->n, (long long)p,
-                              (long long)rc, (long long)h->n, h->g, ap, s),
+        HIPCHK(launch_chirp_pre((const char*)x + esz * h->n * r0, real_in, (long long)h->n, (long long)p,
+                                (long long)rc, (long long)h->n, h->g, ap, s),
                ST_INTERNAL);
         int st = fft_run(p, 0, 1, ap, ap, rc, s);
         if (st) return st;
         HIPCHK(launch_cmul_rows(ap, h->B, (long long)p, (long long)rc, s), ST_INTERNAL);
         if ((st = fft_run(p, 0, -1, ap, ap, rc, s))) return st;
-        HIPCHK(launch_czt_post(ap, (long long)h->n, (long long)p, (long long)h->m, (long long)rc, h->post,
-                               X + h->m * r0, (long long)h->m, s),
+        HIPCHK(launch_chirp_post(ap, (long long)h->n - 1, (long long)p, (long long)h->m, (long long)rc, h->post,
+                                 X + h->m * r0, (long long)h->m, s),
                ST_INTERNAL);
     }
     return ST_OK;

@@ -16,20 +16,10 @@
 
 namespace vvh {
 
-static inline unsigned nblocks(long long count) {
-    long long b = (count + 255) / 256;
-    if (b > 65536) b = 65536;
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
-
-#define GRID_STRIDE(i, count) \
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (count); i += (long long)gridDim.x * blockDim.x)
-
 __global__ void k_hilbert_mask(long long n, const float2* half, float2* full, long long batch,
                                long long half_dist) {
     const long long total = n * batch;
-    GRID_STRIDE(i, total) {
+    VVH_GRID_STRIDE(i, total) {
         const long long f = i / n, k = i - f * n;
         const float2* h = half + f * half_dist;
         float2 z = make_float2(0.0f, 0.0f);
@@ -42,14 +32,14 @@ __global__ void k_hilbert_mask(long long n, const float2* half, float2* full, lo
 
 hipError_t launch_hilbert_mask(long long n, const float2* half, float2* full, long long batch,
                                long long half_dist, hipStream_t s) {
-    hipLaunchKernelGGL(k_hilbert_mask, dim3(nblocks(n * batch)), dim3(256), 0, s, n, half, full, batch,
+    hipLaunchKernelGGL(k_hilbert_mask, dim3(stride_blocks(n * batch)), dim3(256), 0, s, n, half, full, batch,
                        half_dist);
     return hipGetLastError();
 }
 
 __global__ void k_dct2_pre(long long n, const float* x, float* v, long long batch) {
     const long long total = n * batch;
-    GRID_STRIDE(i, total) {
+    VVH_GRID_STRIDE(i, total) {
         const long long f = i / n, m = i - f * n;
         // v[m] = x[2m] for m < n/2 ; v[m] = x[2(n-1-m)+1] for m >= n/2
         const long long src = (m < n / 2) ? 2 * m : 2 * (n - 1 - m) + 1;
@@ -58,7 +48,7 @@ __global__ void k_dct2_pre(long long n, const float* x, float* v, long long batc
 }
 
 hipError_t launch_dct2_pre(long long n, const float* x, float* v, long long batch, hipStream_t s) {
-    hipLaunchKernelGGL(k_dct2_pre, dim3(nblocks(n * batch)), dim3(256), 0, s, n, x, v, batch);
+    hipLaunchKernelGGL(k_dct2_pre, dim3(stride_blocks(n * batch)), dim3(256), 0, s, n, x, v, batch);
     return hipGetLastError();
 }
 
@@ -67,7 +57,7 @@ __global__ void k_dct2_post(long long n, const float2* V, float* X, long long ba
                             const float2* __restrict__ tw4n) {
     const long long total = n * batch;
     const long long nh = n / 2 + 1;
-    GRID_STRIDE(i, total) {
+    VVH_GRID_STRIDE(i, total) {
         const long long f = i / n, k = i - f * n;
         const float2 vk = (k < nh) ? V[f * nh + k] : cconj(V[f * nh + (n - k)]);
         const float2 w = tw4n[k];
@@ -77,7 +67,7 @@ __global__ void k_dct2_post(long long n, const float2* V, float* X, long long ba
 
 hipError_t launch_dct2_post(long long n, const float2* V, float* X, long long batch,
                             const float2* tw4n, hipStream_t s) {
-    hipLaunchKernelGGL(k_dct2_post, dim3(nblocks(n * batch)), dim3(256), 0, s, n, V, X, batch, tw4n);
+    hipLaunchKernelGGL(k_dct2_post, dim3(stride_blocks(n * batch)), dim3(256), 0, s, n, V, X, batch, tw4n);
     return hipGetLastError();
 }
 
@@ -86,7 +76,7 @@ __global__ void k_dct3_pre(long long n, const float* X, float2* V, long long bat
                            const float2* __restrict__ tw4n) {
     const long long nh = n / 2 + 1;
     const long long total = nh * batch;
-    GRID_STRIDE(i, total) {
+    VVH_GRID_STRIDE(i, total) {
         const long long f = i / nh, k = i - f * nh;
         const float a = X[f * n + k];
         const float b = (k == 0) ? 0.0f : X[f * n + (n - k)];
@@ -97,7 +87,7 @@ __global__ void k_dct3_pre(long long n, const float* X, float2* V, long long bat
 
 hipError_t launch_dct3_pre(long long n, const float* X, float2* V, long long batch, const float2* tw4n,
                            hipStream_t s) {
-    hipLaunchKernelGGL(k_dct3_pre, dim3(nblocks((n / 2 + 1) * batch)), dim3(256), 0, s, n, X, V, batch,
+    hipLaunchKernelGGL(k_dct3_pre, dim3(stride_blocks((n / 2 + 1) * batch)), dim3(256), 0, s, n, X, V, batch,
                        tw4n);
     return hipGetLastError();
 }
@@ -105,7 +95,7 @@ hipError_t launch_dct3_pre(long long n, const float* X, float2* V, long long bat
 // x[2m] = v[m], x[2m+1] = v[n-1-m]  (times scale)
 __global__ void k_dct3_post(long long n, const float* v, float* x, long long batch, float scale) {
     const long long total = n * batch;
-    GRID_STRIDE(i, total) {
+    VVH_GRID_STRIDE(i, total) {
         const long long f = i / n, e = i - f * n;
         const long long src = (e % 2 == 0) ? e / 2 : n - 1 - e / 2;
         x[i] = v[f * n + src] * scale;
@@ -114,7 +104,7 @@ __global__ void k_dct3_post(long long n, const float* v, float* x, long long bat
 
 hipError_t launch_dct3_post(long long n, const float* v, float* x, long long batch, float scale,
                             hipStream_t s) {
-    hipLaunchKernelGGL(k_dct3_post, dim3(nblocks(n * batch)), dim3(256), 0, s, n, v, x, batch, scale);
+    hipLaunchKernelGGL(k_dct3_post, dim3(stride_blocks(n * batch)), dim3(256), 0, s, n, v, x, batch, scale);
     return hipGetLastError();
 }
 
@@ -127,7 +117,7 @@ hipError_t launch_dct3_post(long long n, const float* v, float* x, long long bat
 __global__ void k_dct_naive(long long n, int type, int dir, const float* in, float* out,
                             long long batch) {
     const long long total = n * batch;
-    GRID_STRIDE(i, total) {
+    VVH_GRID_STRIDE(i, total) {
         const long long f = i / n, k = i - f * n;
         const float* x = in + f * n;
         double acc = 0.0;
@@ -166,13 +156,13 @@ __global__ void k_dct_naive(long long n, int type, int dir, const float* in, flo
 
 hipError_t launch_dct_naive(long long n, int type, int dir, const float* in, float* out, long long batch,
                             hipStream_t s) {
-    hipLaunchKernelGGL(k_dct_naive, dim3(nblocks(n * batch)), dim3(256), 0, s, n, type, dir, in, out, batch);
+    hipLaunchKernelGGL(k_dct_naive, dim3(stride_blocks(n * batch)), dim3(256), 0, s, n, type, dir, in, out, batch);
     return hipGetLastError();
 }
 
 // NaN/Inf policy (src/core/nan_policy.c): 0 propagate, 1 ignore (->0), 2 error (flag), 3 clamp
 __global__ void k_nan_policy(float* p, long long count, int policy, int* flag) {
-    GRID_STRIDE(i, count) {
+    VVH_GRID_STRIDE(i, count) {
         const float v = p[i];
         if (isfinite(v)) continue;
         if (policy == 1) p[i] = 0.0f;
@@ -183,7 +173,7 @@ __global__ void k_nan_policy(float* p, long long count, int policy, int* flag) {
 
 hipError_t launch_nan_policy(float* p, long long count, int policy, int* flag, hipStream_t s) {
     if (policy == 0 || count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_nan_policy, dim3(nblocks(count)), dim3(256), 0, s, p, count, policy, flag);
+    hipLaunchKernelGGL(k_nan_policy, dim3(stride_blocks(count)), dim3(256), 0, s, p, count, policy, flag);
     return hipGetLastError();
 }
 

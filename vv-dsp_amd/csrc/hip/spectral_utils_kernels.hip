@@ -9,17 +9,9 @@
 
 namespace vvh {
 
-static inline unsigned util_blocks(long long count) {
-    long long b = (count + 255) / 256;
-    if (b > 65536) b = 65536;
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
-
 template <class T>
 __global__ void k_roll_rows(const T* __restrict__ in, T* __restrict__ out, long long n, long long k, long long total) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
+    VVH_GRID_STRIDE(i, total) {
         const long long r = i / n, j = i - r * n;
         long long src = j + k;
         if (src >= n) src -= n;
@@ -34,10 +26,10 @@ hipError_t launch_fftshift(const void* in, void* out, long long n, long long bat
     if (total <= 0) return hipSuccess;
     const long long k = inverse ? n - n / 2 : n / 2;
     if (cpx)
-        hipLaunchKernelGGL(k_roll_rows<float2>, dim3(util_blocks(total)), dim3(256), 0, s, (const float2*)in,
+        hipLaunchKernelGGL(k_roll_rows<float2>, dim3(stride_blocks(total)), dim3(256), 0, s, (const float2*)in,
                            (float2*)out, n, k, total);
     else
-        hipLaunchKernelGGL(k_roll_rows<float>, dim3(util_blocks(total)), dim3(256), 0, s, (const float*)in,
+        hipLaunchKernelGGL(k_roll_rows<float>, dim3(stride_blocks(total)), dim3(256), 0, s, (const float*)in,
                            (float*)out, n, k, total);
     return hipGetLastError();
 }
@@ -45,8 +37,7 @@ hipError_t launch_fftshift(const void* in, void* out, long long n, long long bat
 __global__ void k_phase_wrap(const float* __restrict__ in, float* __restrict__ out, long long total) {
     const float kPi = (float)3.141592653589793238462643383279502884;
     const float kTwoPi = (float)(2.0 * 3.141592653589793238462643383279502884);
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
+    VVH_GRID_STRIDE(i, total) {
         float x = in[i];
         while (x <= -kPi) x += kTwoPi;
         while (x > kPi) x -= kTwoPi;
@@ -56,7 +47,7 @@ __global__ void k_phase_wrap(const float* __restrict__ in, float* __restrict__ o
 
 hipError_t launch_phase_wrap(const float* in, float* out, long long count, hipStream_t s) {
     if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_phase_wrap, dim3(util_blocks(count)), dim3(256), 0, s, in, out, count);
+    hipLaunchKernelGGL(k_phase_wrap, dim3(stride_blocks(count)), dim3(256), 0, s, in, out, count);
     return hipGetLastError();
 }
 

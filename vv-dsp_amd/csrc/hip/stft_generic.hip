@@ -12,8 +12,7 @@ __global__ void k_frame_gather(long long nfft, long long hop, const float* sig, 
                                long long nch, long long ch_stride, long long frames,
                                const float* win, float2* out) {
     const long long total = nch * frames * nfft;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
+    VVH_GRID_STRIDE(i, total) {
         const long long e = i % nfft, fr = (i / nfft) % frames, c = i / (nfft * frames);
         const long long idx = fr * hop + e;
         const float v = (idx < n) ? sig[c * ch_stride + idx] : 0.0f;
@@ -26,16 +25,13 @@ hipError_t launch_frame_gather(long long nfft, long long hop, const float* sig, 
                                float2* out, hipStream_t s) {
     const long long total = nch * frames * nfft;
     if (total <= 0) return hipSuccess;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_frame_gather, dim3((unsigned)blocks), dim3(256), 0, s, nfft, hop, sig, n, nch,
+    hipLaunchKernelGGL(k_frame_gather, dim3(stride_blocks(total)), dim3(256), 0, s, nfft, hop, sig, n, nch,
                        ch_stride, frames, win, out);
     return hipGetLastError();
 }
 
 __global__ void k_magnitude(const float2* in, float* out, long long count) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < count;
-         i += (long long)gridDim.x * blockDim.x) {
+    VVH_GRID_STRIDE(i, count) {
         const float2 v = in[i];
         out[i] = cmag(v.x, v.y);
     }
@@ -43,9 +39,7 @@ __global__ void k_magnitude(const float2* in, float* out, long long count) {
 
 hipError_t launch_magnitude(const float2* in, float* out, long long count, hipStream_t s) {
     if (count <= 0) return hipSuccess;
-    long long blocks = (count + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_magnitude, dim3((unsigned)blocks), dim3(256), 0, s, in, out, count);
+    hipLaunchKernelGGL(k_magnitude, dim3(stride_blocks(count)), dim3(256), 0, s, in, out, count);
     return hipGetLastError();
 }
 
@@ -82,8 +76,7 @@ hipError_t launch_rows_half(const float* in, float* out, long long rows, long lo
 // |X[k]|^2 for k <= nfft/2 of rows [rows][nfft] -> [rows][nfft/2+1]
 __global__ void k_power_half(const float2* in, float* out, long long nfft, long long count) {
     const long long nh = nfft / 2 + 1;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < count;
-         i += (long long)gridDim.x * blockDim.x) {
+    VVH_GRID_STRIDE(i, count) {
         const long long r = i / nh, k = i - r * nh;
         const float2 v = in[r * nfft + k];
         out[i] = __builtin_fmaf(v.x, v.x, v.y * v.y);
@@ -93,9 +86,7 @@ __global__ void k_power_half(const float2* in, float* out, long long nfft, long 
 hipError_t launch_power_half(const float2* in, float* out, long long nfft, long long rows, hipStream_t s) {
     const long long count = rows * (nfft / 2 + 1);
     if (count <= 0) return hipSuccess;
-    long long blocks = (count + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_power_half, dim3((unsigned)blocks), dim3(256), 0, s, in, out, nfft, count);
+    hipLaunchKernelGGL(k_power_half, dim3(stride_blocks(count)), dim3(256), 0, s, in, out, nfft, count);
     return hipGetLastError();
 }
 

@@ -32,14 +32,15 @@ const double2* twiddle_table_d(long long n);
 // Pass-major inter-pass twiddles of the length-n Stockham FFT (fft_core.hpp TwTab).
 const float2* pass_twiddles(int n);
 
-// Two-level table for large n (large_fft.hip): lo[2^lo_bits] ++ hi[n >> lo_bits].
+// Two-level table for large n (fourstep_fft.hip, fft_glue.hip): lo[2^lo_bits] ++ hi[n >> lo_bits].
 const float2* twiddle_split(long long n, int* lo_bits);
 
-// ---- large power-of-two C2C (large_fft.hip): four-step over the fused kernels
+// ---- large power-of-two C2C (fourstep_fft.hip): two HBM passes (fourstep.hpp)
+// up to 2^20, five passes over the fused kernels above
 bool c2c_large_supported(long long n);     // pow2, 8192 .. 2^24
 hipError_t launch_c2c_large(long long n, int fwd, const float2* in, float2* out, long long batch,
                             hipStream_t s);
-// Bluestein (chirp-z) for any n with pow2(2n-1) <= 2^24; same contract as
+// Bluestein (bluestein.hip) for any n with pow2(2n-1) <= 2^24; same contract as
 // launch_dft_naive (real_in promotes real input; nout bins written).
 constexpr long long BLUESTEIN_MIN = 1025;   // below: the f64 O(n^2) DFT (exact-angle, faster at small n)
 bool bluestein_supported(long long n);
@@ -60,7 +61,7 @@ hipError_t launch_stft_mixed(long long nfft, long long hop, int kind, const floa
 // (fft_glue.hip).  fwd: Z [batch][M] -> X [batch][M+1]; inv: X -> V [batch][M].
 hipError_t launch_real_split_fwd(const float2* Z, float2* X, long long M, long long batch, hipStream_t s);
 hipError_t launch_real_split_inv(const float2* X, float2* V, long long M, long long batch, hipStream_t s);
-// real[batch][n] -> complex[batch][n] (imaginary 0)
+// real[batch][n] -> complex[batch][n] (imaginary 0) (fft_glue.hip)
 hipError_t launch_promote_real(const float* in, float2* out, long long count, hipStream_t s);
 
 // ---- mel / MFCC (mel_kernels.hip) ---------------------------------------
@@ -130,6 +131,14 @@ inline int capped_grid(std::atomic<int>& cache, const void* kern, int wg, long l
 }
 // Blocks of a dynamic-walk launch (counters per XCD group): the same number in each of the 8 groups
 inline long long dyn_grid(int cap) { return cap / 8 * 8; }
+// Blocks of 256 threads for an element-wise kernel over `count` items, which
+// walks them with VVH_GRID_STRIDE: one thread per item up to 65536 blocks
+inline unsigned stride_blocks(long long count) {
+    const long long b = (count + 255) / 256;
+    return (unsigned)(b > 65536 ? 65536 : (b < 1 ? 1 : b));
+}
+#define VVH_GRID_STRIDE(i, count) \
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (count); i += (long long)gridDim.x * blockDim.x)
 
 // ---- pow2 register/LDS FFTs (fft_c2c.hip, fft_real.hip; the naive DFT and glue: fft_glue.hip)
 bool c2c_supported(long long n);           // pow2, 2..4096
@@ -239,13 +248,13 @@ hipError_t launch_fir_direct(const float* h, long long taps, const float* x, flo
 // vv_dsp_filtfilt_fir over nch rows (common.c:23-80); tmp: nch * (n + taps - 1) floats
 hipError_t launch_filtfilt(const float* h, long long taps, const float* x, float* y, long long n, long long nch,
                            long long x_stride, long long y_stride, float* tmp, hipStream_t s);
-// overlap-save glue for filters beyond the fused kernels (N > 8192, four-step FFTs):
+// overlap-save glue for filters beyond the fused kernels (N > 8192, four-step FFTs;
+// the product with H is launch_cmul_rows, chirp_glue.hip):
 // rows q < rows of pair p0 + q over (channel, pair) items, ppc pairs per channel,
 // row = z[e] = (x[2j*lout - le + e], x[(2j+1)*lout - le + e]) zero outside [0, n)
 hipError_t launch_fir_long_gather(const float* x, long long n, long long x_stride, long long nfft, long long le,
                                   long long lout, long long ppc, long long p0, long long rows, float2* z,
                                   hipStream_t s);
-hipError_t launch_fir_long_mul(float2* Z, const float2* H, long long nfft, long long rows, hipStream_t s);
 hipError_t launch_fir_long_scatter(const float2* z, float* y, long long n, long long y_stride, long long nfft,
                                    long long le, long long lout, long long ppc, long long p0, long long rows,
                                    hipStream_t s);
@@ -459,15 +468,23 @@ hipError_t launch_dct3_post(long long n, const float* v, float* x, long long bat
 hipError_t launch_dct_naive(long long n, int type, int dir, const float* in, float* out,
                             long long batch, hipStream_t s);
 hipError_t launch_nan_policy(float* p, long long count, int policy, int* flag, hipStream_t s);
-// czt_kernels.hip: chirp-z stages (czt.c:58-178) and the cepstrum family (cepstrum.c, minphase.c)
-hipError_t launch_czt_pre(const void* x, int real_in, long long n, long long p, long long rows, long long in_dist,
-                          const float2* g, float2* a, hipStream_t s);
+// chirp_glue.hip: the element-wise stages of a chirp convolution through a
+// p-point FFT pair (Bluestein, bluestein.hip; the chirp-z transform, czt.c:58-178)
+//   pre:  u[r][i] = x[r][i] * tab[i] for i < n, 0 for n <= i < p (real_in: x is float rows)
+//   cmul: a[r][i] *= B[i] (also the long FIR's product with H)
+//   post: X[r][k] = y[r][off + k] * tab[k], k < nout; _scaled: times scale, rounded after the product
+hipError_t launch_chirp_pre(const void* x, int real_in, long long n, long long p, long long rows, long long in_dist,
+                            const float2* tab, float2* u, hipStream_t s);
 hipError_t launch_cmul_rows(float2* a, const float2* B, long long p, long long rows, hipStream_t s);
-hipError_t launch_czt_post(const float2* a, long long n, long long p, long long m, long long rows, const float2* post,
-                           float2* X, long long out_dist, hipStream_t s);
+hipError_t launch_chirp_post(const float2* y, long long off, long long p, long long nout, long long rows,
+                             const float2* tab, float2* X, long long out_dist, hipStream_t s);
+hipError_t launch_chirp_post_scaled(const float2* y, long long off, long long p, long long nout, long long rows,
+                                    const float2* tab, float2* X, long long out_dist, float scale, hipStream_t s);
+// ceps_stages.hip: the cepstrum family's element-wise stages (cepstrum.c, minphase.c)
 hipError_t launch_log_magnitude(float2* Y, long long count, hipStream_t s);
 hipError_t launch_cepstrum_fold(const float* c, long long n, long long rows, float2* C, hipStream_t s);
 hipError_t launch_exp_real(float2* H, long long count, int dbl, hipStream_t s);
+// czt_kernels.hip (czt_fused.hpp, ceps_fused.hpp):
 // the whole chirp-z chain in one kernel for P <= 4096 (Bs = FFT_P(b) / P)
 bool czt_fused_supported(long long p);
 // the cepstrum family in one pass per row for pow2 n <= 4096 (kind 0 cepstrum,

@@ -1,8 +1,8 @@
 /* cepstrum.c -- real cepstrum and minimum phase on the MI355X backend (C99).
  * Semantics of the reference's src/envelope/cepstrum.c:7-78 and
  * src/envelope/minphase.c:7-31; every transform and element-wise step runs on
- * the GPU (vvhip_cepstrum_*, czt_kernels.hip).  The reference reports any FFT
- * plan failure, n = 0 included, as VV_DSP_ERROR_INTERNAL (cepstrum.c:10-11,
+ * the GPU (vvhip_cepstrum_*; czt_kernels.hip, ceps_stages.hip).  The
+ * reference reports any FFT plan failure, n = 0 included, as VV_DSP_ERROR_INTERNAL (cepstrum.c:10-11,
  * minphase.c:10). */
 #include "vv_dsp/vv_dsp_amd.h"
 #include "vv_dsp/envelope/cepstrum.h"

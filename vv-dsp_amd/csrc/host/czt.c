@@ -2,7 +2,7 @@
  * Semantics of the reference's src/spectral/czt.c: the arc parameters
  * (:22-42) are scalar setup and restate the reference's float arithmetic; the
  * transform (:44-178) runs on the GPU (vvhip_czt_*: chirp pre-multiply, FFT,
- * chirp-spectrum product, inverse FFT, post-multiply; czt_kernels.hip), with
+ * chirp-spectrum product, inverse FFT, post-multiply; chirp_glue.hip), with
  * chirps tabulated in extended precision. */
 #include <math.h>
 #include <stdlib.h>
