@@ -16,6 +16,7 @@
 #include "vv_dsp/filter/savgol.h"
 #include "vv_dsp/features/mel.h"
 #include "vv_dsp/features/pitch.h"
+#include "vv_dsp/features/spectral_shape.h"
 #include "vv_dsp/spectral/czt.h"
 #include "vv_dsp/envelope/cepstrum.h"
 #include "vv_dsp/envelope/minphase.h"
@@ -400,6 +401,43 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_pitch_frames_device(const vv_dsp_real* d_s
                                                           const vv_dsp_pitch_params* params,
                                                           const vv_dsp_pitch_out* out, size_t out_ch_stride,
                                                           size_t cmnd_ch_stride, void* stream);
+/* Per-frame spectral shape descriptors of power rows
+ * (vv_dsp/features/spectral_shape.h, which states every value's definition, its
+ * numerics and the argument checks, made in its order before any device work).
+ * vv_dsp_spectral_shape_out: one pointer per output, NULL = not wanted, else one
+ * value per row.  No output requested: OK, nothing launched; zero rows: OK,
+ * nothing written.  One kernel, one wave per run of rows, all outputs of a row
+ * from one read of it (vvhip_debug_get("STAT_SHAPE_WAVE") counts its launches,
+ * "STAT_SHAPE_VEC16" those that load 16 bytes at a time: a 16-byte aligned
+ * base and a pitch that is a multiple of 4; knob SHAPE_DWORD = 1 forces 4-byte
+ * loads, with the same bits).
+ * _spectral_shape_: `rows` rows of n_fft/2 + 1 powers, row_pitch floats apart
+ * (the packed layout, n_fft/2 + 1, or vv_dsp_stft_power_pitched_device's, e.g.
+ * 544 for n_fft 1024); rows_per_group is the number of frames per channel: row
+ * r starts a group (flux 0) when r % rows_per_group == 0; 0 means one group.
+ * _stft_spectral_shape_: d_signal [nch][n] (ch_stride floats apart) -> planes
+ * [nch][frames], channels out_ch_stride (>= frames, else INVALID_SIZE) values
+ * apart: vv_dsp_stft_power_pitched_device (pitch: n_fft/2 + 1 rounded up to a
+ * whole number of 128 B lines) into stream-ordered scratch, then
+ * _spectral_shape_ with one group per channel -- the values of the two public
+ * calls in sequence, bit for bit.  The scratch holds every row: 4 nch frames
+ * pitch bytes (2.6 GB for 32 channels x 10 min at 16 kHz, n_fft 1024, hop 256),
+ * allocated and freed on the stream.  params->n_fft must equal the handle's
+ * fft_size (INVALID_SIZE). */
+typedef struct vv_dsp_spectral_shape_out {   /* each NULL (not wanted) or one value per row */
+    vv_dsp_real *energy, *centroid, *spread, *skewness, *kurtosis, *flatness, *rolloff, *flux, *crest;
+    uint32_t* peak_bin;
+} vv_dsp_spectral_shape_out;
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_spectral_shape_device(const vv_dsp_real* d_power, size_t rows, size_t row_pitch,
+                                                            size_t rows_per_group,
+                                                            const vv_dsp_spectral_shape_params* params,
+                                                            const vv_dsp_spectral_shape_out* out, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_stft_spectral_shape_device(vv_dsp_stft* h,
+                                                                 const vv_dsp_spectral_shape_params* params,
+                                                                 const vv_dsp_real* d_signal, size_t n, size_t nch,
+                                                                 size_t ch_stride, const vv_dsp_spectral_shape_out* out,
+                                                                 size_t out_ch_stride, void* stream,
+                                                                 size_t* out_frames);
 /* Biquad cascade on `batch` rows of n samples, x_stride / y_stride floats apart
  * (vv_dsp/filter/iir.h, iir.c:21-43).  d_coef [num_stages][5] = b0 b1 b2 a1 a2
  * per stage, one cascade for every row.  d_state [batch][num_stages][2] = z1 z2

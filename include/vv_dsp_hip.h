@@ -32,6 +32,8 @@
  *   vvhip_stats_* / _autocorrelation_* / _cross_correlation_*: src/core/core.c:42-108,
  *                  src/core/stats.c:10-139
  *   vvhip_pitch_*: no reference source; include/vv_dsp/features/pitch.h defines it
+ *   vvhip_shape_* / _stft_shape_*: no reference source;
+ *                  include/vv_dsp/features/spectral_shape.h defines them
  */
 #ifndef VV_DSP_HIP_H
 #define VV_DSP_HIP_H
@@ -416,6 +418,41 @@ int vvhip_pitch_frames_device(const float* d_signal, size_t n, size_t nch, size_
                               const vvhip_pitch_params* params, const vvhip_pitch_out* out, size_t out_ch_stride,
                               size_t cmnd_ch_stride, void* stream);
 int vvhip_pitch_host(const float* x, size_t n, const vvhip_pitch_params* params, float* f0, float* aperiodicity);
+
+/* ---- Per-frame spectral shape (include/vv_dsp/features/spectral_shape.h: the
+ * definitions and the checks, made in its order before any device work) ----
+ * vvhip_shape_params / vvhip_shape_out / vvhip_shape_values: the layouts of
+ * vv_dsp_spectral_shape_params, _out and _values.  _shape_: `rows` rows of
+ * n_fft/2 + 1 powers row_pitch floats apart, groups of rows_per_group rows (0: one
+ * group), value of row r at out + r.  _stft_shape_: the handle's power rows
+ * (vvhip_stft_power_pitched_device, whole 128 B lines per row) into
+ * stream-ordered scratch, then _shape_ with one group per channel, value of
+ * (ch, frame) at out + ch * out_ch_stride + frame.  No output wanted: 0, nothing
+ * launched.  One kernel, one wave per run of rows ("STAT_SHAPE_WAVE" counts its
+ * launches, "STAT_SHAPE_VEC16" those with 16-byte loads; shape_kernels.hip);
+ * knob SHAPE_DWORD = 1 forces 4-byte loads, with
+ * the same bits.  _host: one row (and its predecessor, or NULL) in host memory. */
+typedef struct vvhip_shape_params {
+    size_t n_fft;
+    float sample_rate;
+    int magnitude;
+    size_t k_min, k_max;
+    float rolloff, floor;
+} vvhip_shape_params;
+typedef struct vvhip_shape_out {
+    float *energy, *centroid, *spread, *skewness, *kurtosis, *flatness, *rolloff, *flux, *crest;
+    uint32_t* peak_bin;
+} vvhip_shape_out;
+typedef struct vvhip_shape_values {
+    float energy, centroid, spread, skewness, kurtosis, flatness, rolloff, flux, crest;
+    uint32_t peak_bin;
+} vvhip_shape_values;
+int vvhip_shape_device(const float* d_power, size_t rows, size_t row_pitch, size_t rows_per_group,
+                       const vvhip_shape_params* params, const vvhip_shape_out* out, void* stream);
+int vvhip_stft_shape_device(vvhip_stft* h, const vvhip_shape_params* params, const float* d_signal, size_t n,
+                            size_t nch, size_t ch_stride, const vvhip_shape_out* out, size_t out_ch_stride,
+                            void* stream);
+int vvhip_shape_host(const float* row, const float* prev, const vvhip_shape_params* params, vvhip_shape_values* out);
 
 /* ---- Spectral utilities (src/spectral/utils.c:5-73) ----
  * `batch` contiguous rows of n: fftshift (inverse 0) / ifftshift (inverse 1) of

@@ -18,11 +18,11 @@ enum Knob : int {
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
-    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_COUNT
+    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_SHAPE_DWORD, KNOB_COUNT
 };
 long long knob(Knob k, long long dflt);
 // launches of the paths the tests must see taken (vvhip_debug_get("STAT_..."))
-enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_PITCH_WAVE, STAT_COUNT };
+enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_PITCH_WAVE, STAT_SHAPE_WAVE, STAT_SHAPE_VEC16, STAT_COUNT };
 void stat_inc(Stat s);
 
 // Device-resident W_N^k = exp(-2*pi*i*k/N) table, k < N, f32 rounded from double.
@@ -404,6 +404,39 @@ struct PitchOut {
 // The row sits in LDS as f64 where four rows fit 64 KiB, as f32 beyond or with
 // f32_rows (knob PITCH_F32 = 1): the conversion is exact, the bits are the same.
 hipError_t launch_pitch(const FrameSrc& src, const PitchCfg& cfg, const PitchOut& out, bool f32_rows, hipStream_t s);
+
+// ---- per-frame spectral shape (shape_kernels.hip), include/vv_dsp/features/spectral_shape.h ----
+constexpr int SHAPE_MAX_BINS = 8193;             // K = n_fft / 2 + 1 of a row
+// the outputs, in the order of vv_dsp_spectral_shape_out's members; bit k of a mask = output k
+enum ShapeBit : int {
+    SHAPE_ENERGY, SHAPE_CENTROID, SHAPE_SPREAD, SHAPE_SKEW, SHAPE_KURT, SHAPE_FLATNESS, SHAPE_ROLLOFF, SHAPE_FLUX,
+    SHAPE_CREST, SHAPE_PEAK, SHAPE_NOUT
+};
+// the parameters as the kernel uses them (shim_shape.hip checks them)
+struct ShapeCfg {
+    int K = 0, k_min = 0, k_max = 0, magnitude = 0;
+    double sample_rate = 0.0, n_fft = 0.0, rolloff = 0.0;
+    float floor = 0.0f;
+};
+// Value of row r = g * rows_per_group + f at p[k] + g * group_stride + f; p[k] null: not wanted.
+struct ShapeOut {
+    void* p[SHAPE_NOUT] = {};
+    long long group_stride = 0;
+    unsigned mask() const {
+        unsigned m = 0;
+        for (int k = 0; k < SHAPE_NOUT; ++k)
+            if (p[k]) m |= 1u << k;
+        return m;
+    }
+};
+// `rows` rows of cfg.K weights, row_pitch floats apart, in groups of rows_per_group
+// (> 0) consecutive rows: one wave per run of rows of one group, one launch;
+// nothing wanted or no rows: nothing launched.  dword (knob SHAPE_DWORD = 1):
+// 4-byte loads even where the rows allow 16-byte ones (the same bits).
+// whether rows at this base and pitch can be loaded 16 bytes at a time (every row 16-byte aligned)
+bool shape_rows_vec16(const float* rows_ptr, long long row_pitch);
+hipError_t launch_shape(const float* rows_ptr, long long rows, long long row_pitch, long long rows_per_group,
+                        const ShapeCfg& cfg, const ShapeOut& out, bool dword, hipStream_t s);
 
 // ---- biquad cascade (iir_kernels.hip), src/filter/iir.c:21-43 -----------------
 constexpr int IIR_MAX_STAGES = 8;        // stages one walk holds in registers; longer cascades run in groups

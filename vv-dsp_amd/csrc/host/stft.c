@@ -166,6 +166,9 @@ vv_dsp_status vv_dsp_stft_reconstruct_device(vv_dsp_stft* h, const vv_dsp_cpx* d
                                                         d_norm_add, stream);
 }
 
+/* the device side of a handle, for the entry points that live in other files (spectral_shape.c) */
+__attribute__((visibility("hidden"))) vvhip_stft* vv_amd_stft_device_handle(const vv_dsp_stft* h) { return h->dev; }
+
 /* ---- multi-GPU layout (vv_dsp_amd.h) ---- */
 vv_dsp_status vv_dsp_stft_get_sizes(const vv_dsp_stft* h, size_t* fft_size, size_t* hop_size) {
     if (!h) return VV_DSP_ERROR_NULL_POINTER;

@@ -54,6 +54,21 @@ class PitchOut(C.Structure):
 PITCH_NAMES = tuple(name for name, _ in PitchOut._fields_)
 
 
+class SpectralShapeParams(C.Structure):
+    """vv_dsp_spectral_shape_params (vv_dsp/features/spectral_shape.h)"""
+    _fields_ = [("n_fft", C.c_size_t), ("sample_rate", C.c_float), ("magnitude", C.c_int), ("k_min", C.c_size_t),
+                ("k_max", C.c_size_t), ("rolloff", C.c_float), ("floor", C.c_float)]
+
+
+class SpectralShapeOut(C.Structure):
+    """vv_dsp_spectral_shape_out: one device pointer per output, NULL = not wanted"""
+    _fields_ = [(name, C.c_void_p) for name in ("energy", "centroid", "spread", "skewness", "kurtosis", "flatness",
+                                                 "rolloff", "flux", "crest", "peak_bin")]
+
+
+SHAPE_NAMES = tuple(name for name, _ in SpectralShapeOut._fields_)
+
+
 class VvError(RuntimeError):
     pass
 
@@ -155,6 +170,11 @@ def lib():
     L.vv_dsp_pitch_device.argtypes = [_vp, _sz, _sz, _sz, C.POINTER(PitchParams), C.POINTER(PitchOut), _sz, _vp]
     L.vv_dsp_pitch_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, C.POINTER(PitchParams),
                                              C.POINTER(PitchOut), _sz, _sz, _vp]
+    L.vv_dsp_spectral_shape.argtypes = [_vp, _vp, C.POINTER(SpectralShapeParams), _vp]
+    L.vv_dsp_spectral_shape_device.argtypes = [_vp, _sz, _sz, _sz, C.POINTER(SpectralShapeParams),
+                                               C.POINTER(SpectralShapeOut), _vp]
+    L.vv_dsp_stft_spectral_shape_device.argtypes = [_vp, C.POINTER(SpectralShapeParams), _vp, _sz, _sz, _sz,
+                                                    C.POINTER(SpectralShapeOut), _sz, _vp, C.POINTER(_sz)]
     L.vv_dsp_iir_apply_device.argtypes = [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]
     L.vv_dsp_savgol_coeffs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, _vp]
     L.vv_dsp_savgol_device.argtypes = [_vp, _sz, _sz, _sz, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp, _sz,
@@ -325,6 +345,21 @@ class Stft:
                    "stft_power_pitched_device")
         assert nf.value == fr
         return out if sig.dim() == 2 else out[0]
+
+    def spectral_shape(self, sig, params, what, stream=None):
+        """sig: (nch, n) or (n,) float32 -> {name: (nch, frames) or (frames,)} for the names
+        in `what` (SHAPE_NAMES): power(pitch=...) -> spectral_shape() in one call, the
+        power rows in stream-ordered scratch (vv_dsp_stft_spectral_shape_device)."""
+        sig2, nch, n = _signal(sig, "stft spectral_shape")
+        fr = self.frames(n)
+        planes, out = _shape_planes(params, what, (nch, fr), sig.device, "stft spectral_shape")
+        if planes and nch:
+            nf = _sz(0)
+            _check(lib().vv_dsp_stft_spectral_shape_device(self.h, C.byref(params), _vp(sig2.data_ptr()), n, nch,
+                                                           sig2.stride(0), C.byref(out), fr, _stream(stream),
+                                                           C.byref(nf)), "stft_spectral_shape_device")
+            assert nf.value == fr
+        return _planes_of(planes, sig)
 
     def frames_range(self, sig, frame0, nframes, kind=0, out=None, stream=None):
         """Rows of frames [frame0, frame0 + nframes) of sig's spectrogram (one shard
@@ -875,6 +910,55 @@ def pitch_frames(sig, frame_len, hop, params, what, window=None, center=False, s
                                                 C.byref(params), C.byref(out), fr, fr * (tau_max + 1),
                                                 _stream(stream)), "pitch_frames_device")
     return _planes_of(planes, sig)
+
+
+def _shape_planes(params, what, shape, device, who):
+    """the output tensors of `what` and the vv_dsp_spectral_shape_out that points at them"""
+    if not isinstance(params, SpectralShapeParams):
+        raise VvError(f"{who}: params must be a SpectralShapeParams")
+    if isinstance(what, str):
+        what = (what,)
+    planes, out = {}, SpectralShapeOut()
+    for name in what:
+        if name not in SHAPE_NAMES:
+            raise VvError(f"{who}: unknown output {name!r} (one of {', '.join(SHAPE_NAMES)})")
+        if name not in planes:
+            planes[name] = torch.empty(shape, dtype=torch.int32 if name == "peak_bin" else torch.float32,
+                                       device=device)
+            setattr(out, name, planes[name].data_ptr())
+    return planes, out
+
+
+def spectral_shape(power, params, what, rows_per_group=0, stream=None):
+    """Spectral shape descriptors of float32 device power rows
+    (vv_dsp/features/spectral_shape.h): power (rows, pitch) or (ch, frames, pitch), the
+    rows power.stride(-2) >= n_fft//2 + 1 floats apart (bins 0..n_fft//2 of each are
+    read) -> {name: tensor (rows,) or (ch, frames)} for the names in `what`
+    (SHAPE_NAMES), all from one launch; peak_bin is an int32 view of the uint32 values.
+    A (ch, frames, pitch) tensor is ch groups of `frames` rows (flux is 0 at each
+    channel's first frame); for (rows, pitch), rows_per_group rows form a group (0: one)."""
+    if not isinstance(params, SpectralShapeParams):
+        raise VvError("spectral_shape: params must be a SpectralShapeParams")
+    if power.dim() not in (2, 3) or power.dtype != torch.float32 or not power.is_cuda:
+        raise VvError("spectral_shape: float32 device rows (rows, pitch) or (ch, frames, pitch)")
+    nb = params.n_fft // 2 + 1
+    lead = tuple(power.shape[:-1])
+    rows = 1
+    for d in lead:
+        rows *= d
+    pitch = power.stride(-2) if power.shape[-2] > 1 else power.shape[-1]
+    if power.shape[-1] < nb or (power.shape[-1] > 1 and power.stride(-1) != 1) or pitch < nb:
+        raise VvError(f"spectral_shape: rows of {power.shape[-1]} floats, pitch {pitch}, for {nb} bins")
+    if power.dim() == 3:
+        if power.shape[0] > 1 and power.stride(0) != power.shape[1] * pitch:
+            raise VvError("spectral_shape: channels must follow each other, frames x pitch floats apart")
+        rows_per_group = power.shape[1]
+    planes, out = _shape_planes(params, what, lead, power.device, "spectral_shape")
+    if planes and rows:
+        _check(lib().vv_dsp_spectral_shape_device(_vp(power.data_ptr()), rows, pitch, rows_per_group,
+                                                  C.byref(params), C.byref(out), _stream(stream)),
+               "spectral_shape_device")
+    return planes
 
 
 def autocorrelation(x, r_len, biased=False, stream=None):
