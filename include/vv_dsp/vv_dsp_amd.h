@@ -18,6 +18,7 @@
 #include "vv_dsp/features/pitch.h"
 #include "vv_dsp/features/spectral_shape.h"
 #include "vv_dsp/spectral/czt.h"
+#include "vv_dsp/spectral/phase_vocoder.h"
 #include "vv_dsp/envelope/cepstrum.h"
 #include "vv_dsp/envelope/minphase.h"
 #include "vv_dsp/envelope/lpc.h"
@@ -438,6 +439,52 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_stft_spectral_shape_device(vv_dsp_stft* h,
                                                                  size_t ch_stride, const vv_dsp_spectral_shape_out* out,
                                                                  size_t out_ch_stride, void* stream,
                                                                  size_t* out_frames);
+/* Phase vocoder: time-stretch of STFT rows (vv_dsp/spectral/phase_vocoder.h, which
+ * states every value's definition, the order of the phase sum, and the argument
+ * checks, made in its order before any device work).  d_spec [nch][T][n_fft]
+ * complex rows, channels spec_ch_stride vv_dsp_cpx apart (>= T n_fft), only bins
+ * 0 .. n_fft/2 read -> d_out [nch][m][n_fft], channels out_ch_stride vv_dsp_cpx
+ * apart (>= m n_fft), every bin of rows 0 .. m - 1 written and nothing else.
+ * _uniform_: output row j at start + j step; _device: at d_pos[j], m floats on the
+ * device shared by all channels.  Equal positions give equal bits.  Three
+ * launches: the segments' phase totals, their scan, the rows
+ * (vvhip_debug_get("STAT_PVOC_ROWS") counts the calls that launched them);
+ * stream-ordered scratch of 8 nch (n_fft/2 + 1) (segments + 1) bytes.  Knob
+ * PVOC_PLANE = 1 (for timing; the same bits): a fourth launch stores the rows'
+ * phases in 8 nch T (n_fft/2 + 1) more bytes of scratch and the walks read them
+ * instead of calling atan2 a second time. */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_phase_vocoder_uniform_device(const vv_dsp_cpx* d_spec, size_t T, size_t n_fft,
+                                                                   size_t nch, size_t spec_ch_stride, double start,
+                                                                   double step, size_t m, vv_dsp_cpx* d_out,
+                                                                   size_t out_ch_stride, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_phase_vocoder_device(const vv_dsp_cpx* d_spec, size_t T, size_t n_fft, size_t nch,
+                                                           size_t spec_ch_stride, const vv_dsp_real* d_pos, size_t m,
+                                                           vv_dsp_cpx* d_out, size_t out_ch_stride, void* stream);
+/* Time-stretch, signal to signal: d_signal [nch][n] (ch_stride floats apart) ->
+ * d_out [nch][out_len] (out_ch_stride floats apart, >= out_len), a signal `rate`
+ * times as fast at the same pitch (rate 0.5: twice as long).  With T the handle's
+ * frame count of n samples, m the number of j >= 0 with (double)j rate < (double)T
+ * and out_len = (m - 1) hop + fft_size: vv_dsp_stft_spectrum_device, the vocoder at
+ * start 0 and step rate, vv_dsp_stft_reconstruct_device of each channel's m rows
+ * into zeroed out and norm, then y[i] = norm[i] > VV_DSP_PVOC_NORM_FLOOR ?
+ * out[i] / norm[i] : 0 -- the values of the public calls in sequence, bit for bit.
+ * The rows live in stream-ordered scratch, a group of channels at a time (as
+ * many as fit 1 GiB, at least one; knob PVOC_GROUP = k: k channels per group; the
+ * result does not depend on it).  Checks in this order: NULL handle, signal or
+ * out; fft_size < 2, ch_stride < n or out_ch_stride < out_len -- INVALID_SIZE; a
+ * rate that is not finite or <= 0 -- OUT_OF_RANGE; the vocoder's limits --
+ * UNSUPPORTED.  out_len depends on the rate, so out_ch_stride is checked for a
+ * valid rate only: a bad rate with a short out_ch_stride gives OUT_OF_RANGE.
+ * ch_stride is checked for nch > 1 only, as the neighbouring STFT calls check
+ * theirs (one channel has no stride to step over); out_ch_stride, like the
+ * strides of vv_dsp_phase_vocoder_*_device, is checked for one channel too.  *out_len (may be NULL) is set once every check has passed.
+ * _length: m and out_len for n samples (either pointer may be NULL), to size d_out. */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_stft_time_stretch_length(const vv_dsp_stft* h, size_t n, double rate,
+                                                               size_t* out_rows, size_t* out_len);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_stft_time_stretch_device(vv_dsp_stft* h, const vv_dsp_real* d_signal, size_t n,
+                                                               size_t nch, size_t ch_stride, double rate,
+                                                               vv_dsp_real* d_out, size_t out_ch_stride, void* stream,
+                                                               size_t* out_len);
 /* Biquad cascade on `batch` rows of n samples, x_stride / y_stride floats apart
  * (vv_dsp/filter/iir.h, iir.c:21-43).  d_coef [num_stages][5] = b0 b1 b2 a1 a2
  * per stage, one cascade for every row.  d_state [batch][num_stages][2] = z1 z2

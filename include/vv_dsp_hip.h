@@ -34,6 +34,8 @@
  *   vvhip_pitch_*: no reference source; include/vv_dsp/features/pitch.h defines it
  *   vvhip_shape_* / _stft_shape_*: no reference source;
  *                  include/vv_dsp/features/spectral_shape.h defines them
+ *   vvhip_pvoc_* / _stft_stretch_*: no reference source;
+ *                  include/vv_dsp/spectral/phase_vocoder.h defines them
  */
 #ifndef VV_DSP_HIP_H
 #define VV_DSP_HIP_H
@@ -69,8 +71,8 @@ const char* vvhip_last_error(void);
  *       "STAT_MEL_SPLIT", "STAT_RESAMPLE_TABLE", "STAT_RESAMPLE_GENERIC",
  *       "STAT_LPC_WAVE", "STAT_LPC_GENERIC", "STAT_IIR_EXACT",
  *       "STAT_IIR_CHUNKED", "STAT_STATS_WAVE", "STAT_STATS_LONG",
- *       "STAT_INTERP_ONE", "STAT_INTERP_ROWS", "STAT_PITCH_WAVE": launches of
- *       that path since the last clear);
+ *       "STAT_INTERP_ONE", "STAT_INTERP_ROWS", "STAT_PITCH_WAVE",
+ *       "STAT_PVOC_ROWS": launches of that path since the last clear);
  *       -2 unknown.
  * The environment is read once per process, and only with VVHIP_AB=1 set. */
 int vvhip_debug_set(const char* name, long long value);
@@ -453,6 +455,27 @@ int vvhip_stft_shape_device(vvhip_stft* h, const vvhip_shape_params* params, con
                             size_t nch, size_t ch_stride, const vvhip_shape_out* out, size_t out_ch_stride,
                             void* stream);
 int vvhip_shape_host(const float* row, const float* prev, const vvhip_shape_params* params, vvhip_shape_values* out);
+
+/* ---- Phase vocoder (include/vv_dsp/spectral/phase_vocoder.h: the definition and
+ * the checks, made in its order before any device work) ----
+ * d_spec [nch][T][n_fft] float pairs, channels spec_ch_stride pairs apart ->
+ * d_out [nch][m][n_fft], channels out_ch_stride pairs apart.  d_pos null: output
+ * row j at start + j step (check 3 applies); else at d_pos[j].  Three launches
+ * (pvoc_kernels.hip; "STAT_PVOC_ROWS" counts the calls that made them; knob
+ * PVOC_PLANE = 1: a fourth launch stores the rows' phases in an f64 plane the
+ * walks read, with the same bits).
+ * _host: one channel in host memory, uniform form.
+ * _stft_stretch_: signal [nch][n] -> signal [nch][out_len] through the handle's
+ * spectrum rows, the vocoder at start 0 and step rate, the overlap-add and the
+ * division by the summed squared window, in channel groups (knob PVOC_GROUP).
+ * _stretch_length: rows m and samples out_len of that call. */
+int vvhip_pvoc_device(const float* d_spec, size_t T, size_t n_fft, size_t nch, size_t spec_ch_stride,
+                      const float* d_pos, double start, double step, size_t m, float* d_out, size_t out_ch_stride,
+                      void* stream);
+int vvhip_pvoc_host(const float* spec, size_t T, size_t n_fft, double start, double step, size_t m, float* out);
+int vvhip_stft_stretch_length(size_t n, size_t nfft, size_t hop, double rate, size_t* rows, size_t* out_len);
+int vvhip_stft_stretch_device(vvhip_stft* h, const float* d_signal, size_t n, size_t nch, size_t ch_stride,
+                              double rate, float* d_out, size_t out_ch_stride, void* stream, size_t* out_len);
 
 /* ---- Spectral utilities (src/spectral/utils.c:5-73) ----
  * `batch` contiguous rows of n: fftshift (inverse 0) / ifftshift (inverse 1) of

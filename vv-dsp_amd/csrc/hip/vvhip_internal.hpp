@@ -18,11 +18,11 @@ enum Knob : int {
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
-    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_SHAPE_DWORD, KNOB_COUNT
+    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_SHAPE_DWORD, KNOB_PVOC_GROUP, KNOB_PVOC_PLANE, KNOB_COUNT
 };
 long long knob(Knob k, long long dflt);
 // launches of the paths the tests must see taken (vvhip_debug_get("STAT_..."))
-enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_PITCH_WAVE, STAT_SHAPE_WAVE, STAT_SHAPE_VEC16, STAT_COUNT };
+enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_PITCH_WAVE, STAT_SHAPE_WAVE, STAT_SHAPE_VEC16, STAT_PVOC_ROWS, STAT_COUNT };
 void stat_inc(Stat s);
 
 // Device-resident W_N^k = exp(-2*pi*i*k/N) table, k < N, f32 rounded from double.
@@ -437,6 +437,36 @@ struct ShapeOut {
 bool shape_rows_vec16(const float* rows_ptr, long long row_pitch);
 hipError_t launch_shape(const float* rows_ptr, long long rows, long long row_pitch, long long rows_per_group,
                         const ShapeCfg& cfg, const ShapeOut& out, bool dword, hipStream_t s);
+
+// ---- phase vocoder (pvoc_kernels.hip), include/vv_dsp/spectral/phase_vocoder.h ----
+constexpr int PVOC_SEGMENT = 32;                  // VV_DSP_PVOC_SEGMENT: output rows per segment of the phase sum
+constexpr long long PVOC_MAX_FFT = 1ll << 24;     // VV_DSP_PVOC_MAX_FFT
+constexpr float PVOC_NORM_FLOOR = 1e-8f;          // VV_DSP_PVOC_NORM_FLOOR
+struct PvocArgs {
+    const float2* in = nullptr;    // [nch][T][n_fft], channels in_ch_stride apart
+    float2* out = nullptr;         // [nch][m][n_fft], channels out_ch_stride apart
+    long long T = 0, n_fft = 0, nch = 0, m = 0, in_ch_stride = 0, out_ch_stride = 0;
+    const float* pos = nullptr;    // m positions, or null: start + j * step
+    double start = 0.0, step = 0.0;
+    // scratch of pvoc_scratch_doubles(): [nch][nseg][K] segment totals, which the
+    // scan turns into the segments' bases, then [nch][K] the phase of row 0
+    double* work = nullptr;
+    // null, or [nch][T][K] doubles for the rows' phases (knob PVOC_PLANE)
+    const double* plane = nullptr;
+};
+constexpr long long pvoc_segments(long long m) { return (m + PVOC_SEGMENT - 1) / PVOC_SEGMENT; }
+inline size_t pvoc_scratch_doubles(long long n_fft, long long nch, long long m) {
+    return (size_t)nch * (size_t)(n_fft / 2 + 1) * (size_t)(pvoc_segments(m) + 1);
+}
+// whether one launch takes these sizes (the header's check 4 and the grid's limits)
+bool pvoc_supported(long long T, long long n_fft, long long nch, long long m);
+// whether the phase plane's kernel takes these sizes
+bool pvoc_plane_supported(long long T, long long n_fft, long long nch);
+// totals, scan, rows on stream s; m > 0, nch > 0, supported sizes
+hipError_t launch_pvoc(const PvocArgs& a, hipStream_t s);
+// y[c][i] = norm[c][i] > PVOC_NORM_FLOOR ? y[c][i] / norm[c][i] : 0 for i < len (norm rows contiguous)
+hipError_t launch_pvoc_normalize(float* y, long long y_stride, const float* norm, long long len, long long nch,
+                                 hipStream_t s);
 
 // ---- biquad cascade (iir_kernels.hip), src/filter/iir.c:21-43 -----------------
 constexpr int IIR_MAX_STAGES = 8;        // stages one walk holds in registers; longer cascades run in groups

@@ -175,6 +175,13 @@ def lib():
                                                C.POINTER(SpectralShapeOut), _vp]
     L.vv_dsp_stft_spectral_shape_device.argtypes = [_vp, C.POINTER(SpectralShapeParams), _vp, _sz, _sz, _sz,
                                                     C.POINTER(SpectralShapeOut), _sz, _vp, C.POINTER(_sz)]
+    L.vv_dsp_phase_vocoder.argtypes = [_vp, _sz, _sz, C.c_double, C.c_double, _sz, _vp]
+    L.vv_dsp_phase_vocoder_uniform_device.argtypes = [_vp, _sz, _sz, _sz, _sz, C.c_double, C.c_double, _sz, _vp, _sz,
+                                                      _vp]
+    L.vv_dsp_phase_vocoder_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _vp]
+    L.vv_dsp_stft_time_stretch_length.argtypes = [_vp, _sz, C.c_double, C.POINTER(_sz), C.POINTER(_sz)]
+    L.vv_dsp_stft_time_stretch_device.argtypes = [_vp, _vp, _sz, _sz, _sz, C.c_double, _vp, _sz, _vp, C.POINTER(_sz)]
+    L.vvhip_stft_stretch_length.argtypes = [_sz, _sz, _sz, C.c_double, C.POINTER(_sz), C.POINTER(_sz)]
     L.vv_dsp_iir_apply_device.argtypes = [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]
     L.vv_dsp_savgol_coeffs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, _vp]
     L.vv_dsp_savgol_device.argtypes = [_vp, _sz, _sz, _sz, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp, _sz,
@@ -360,6 +367,35 @@ class Stft:
                                                            C.byref(nf)), "stft_spectral_shape_device")
             assert nf.value == fr
         return _planes_of(planes, sig)
+
+    def time_stretch_length(self, n, rate):
+        """(rows, samples) of time_stretch() of an n-sample signal (vv_dsp_stft_time_stretch_length)"""
+        m, ln = _sz(0), _sz(0)
+        _check(lib().vv_dsp_stft_time_stretch_length(self.h, n, float(rate), C.byref(m), C.byref(ln)),
+               "stft_time_stretch_length")
+        return m.value, ln.value
+
+    def time_stretch(self, sig, rate, out=None, stream=None):
+        """sig: (nch, n) or (n,) float32 -> (nch, out_len) or (out_len,), `rate` times as
+        fast at the same pitch: spectrogram(complex_out=True) -> phase_vocoder(step=rate) ->
+        reconstruct() into zeros -> out / norm, in one call with the rows in stream-ordered
+        scratch (vv_dsp_stft_time_stretch_device), bit-identical to those steps."""
+        sig2, nch, n = _signal(sig, "stft time_stretch")
+        _, ln = self.time_stretch_length(n, rate)
+        if out is None:
+            out = torch.empty((nch, ln) if sig.dim() == 2 else (ln,), dtype=torch.float32, device=sig.device)
+        out2 = out if out.dim() == 2 else out.unsqueeze(0)
+        if out.dim() != sig.dim() or out2.dtype != torch.float32 or not out2.is_cuda or out2.shape != (nch, ln) or \
+                (ln > 1 and out2.stride(1) != 1):
+            raise VvError(f"stft time_stretch output: float32 device rows of shape ({nch}, {ln})")
+        got = _sz(0)
+        if nch:
+            _check(lib().vv_dsp_stft_time_stretch_device(self.h, _vp(sig2.data_ptr()), n, nch, sig2.stride(0),
+                                                         float(rate), _vp(out2.data_ptr()),
+                                                         out2.stride(0) if nch > 1 else ln, _stream(stream),
+                                                         C.byref(got)), "stft_time_stretch_device")
+            assert got.value == ln
+        return out
 
     def frames_range(self, sig, frame0, nframes, kind=0, out=None, stream=None):
         """Rows of frames [frame0, frame0 + nframes) of sig's spectrogram (one shard
@@ -959,6 +995,67 @@ def spectral_shape(power, params, what, rows_per_group=0, stream=None):
                                                   C.byref(params), C.byref(out), _stream(stream)),
                "spectral_shape_device")
     return planes
+
+
+def _pvoc_rows(t, n_fft, who):
+    """(t3, nch, rows, ch_stride) of complex64 device rows (rows, n_fft) or (nch, rows, n_fft):
+    unit bin stride, rows n_fft apart, channels t.stride(0) >= rows * n_fft apart"""
+    if t.dim() not in (2, 3) or t.dtype != torch.complex64 or not t.is_cuda:
+        raise VvError(f"{who}: complex64 device rows (rows, n_fft) or (nch, rows, n_fft)")
+    t3 = t if t.dim() == 3 else t.unsqueeze(0)
+    nch, rows, width = t3.shape
+    if width != n_fft or (width > 1 and t3.stride(2) != 1) or (rows > 1 and t3.stride(1) != n_fft):
+        raise VvError(f"{who}: rows of {width} bins, {t3.stride(1)} apart, for n_fft {n_fft}")
+    ch_stride = t3.stride(0) if nch > 1 else rows * n_fft
+    if ch_stride < rows * n_fft:
+        raise VvError(f"{who}: channels {ch_stride} apart, below rows x n_fft")
+    return t3, nch, rows, ch_stride
+
+
+def phase_vocoder(spec, n_fft, start=0.0, step=1.0, m=None, pos=None, out=None, stream=None):
+    """Phase vocoder (vv_dsp/spectral/phase_vocoder.h): complex64 device rows spec (T, n_fft)
+    or (nch, T, n_fft), as Stft.spectrogram(complex_out=True) gives them, -> (m, n_fft) or
+    (nch, m, n_fft), output row j at analysis position start + j * step, or at pos[j] when
+    pos (m float32 on the device, shared by the channels) is given.  m defaults to the
+    number of positions below T.  The rows feed Stft.reconstruct as they are."""
+    n_fft = int(n_fft)
+    if n_fft < 2:
+        raise VvError(f"phase_vocoder: n_fft {n_fft}")
+    spec3, nch, T, in_stride = _pvoc_rows(spec, n_fft, "phase_vocoder input")
+    if pos is not None:
+        if pos.dim() != 1 or m not in (None, pos.shape[0]):
+            raise VvError("phase_vocoder: pos must be one row of m positions")
+        m = pos.shape[0]
+        _expect(pos, torch.float32, m, "phase_vocoder positions")
+    elif m is None:
+        if not step > 0.0:
+            raise VvError("phase_vocoder: m is needed when step is not positive")
+        m = max(0, int((T - start) / step))
+        while start + m * step < T:
+            m += 1
+        while m > 0 and not start + (m - 1) * step < T:
+            m -= 1
+    m = int(m)
+    if m < 0:
+        raise VvError(f"phase_vocoder: m {m}")
+    if out is None:
+        out = torch.empty((nch, m, n_fft), dtype=torch.complex64, device=spec.device)
+        if spec.dim() == 2:
+            out = out[0]
+    out3, och, om, out_stride = _pvoc_rows(out, n_fft, "phase_vocoder output")
+    if och != nch or om != m or out.dim() != spec.dim():
+        raise VvError(f"phase_vocoder output: shape {tuple(out.shape)} for {nch} channels of {m} rows")
+    if m == 0 or nch == 0:          # nothing to write (and the empty tensors have no storage to point at)
+        return out
+    if pos is None:
+        st = lib().vv_dsp_phase_vocoder_uniform_device(_vp(spec3.data_ptr()), T, n_fft, nch, in_stride, float(start),
+                                                       float(step), m, _vp(out3.data_ptr()), out_stride,
+                                                       _stream(stream))
+    else:
+        st = lib().vv_dsp_phase_vocoder_device(_vp(spec3.data_ptr()), T, n_fft, nch, in_stride, _ptr(pos), m,
+                                               _vp(out3.data_ptr()), out_stride, _stream(stream))
+    _check(st, "phase_vocoder_device")
+    return out
 
 
 def autocorrelation(x, r_len, biased=False, stream=None):
