@@ -300,7 +300,13 @@ class FftPlan:
 
 
 class Stft:
-    """STFT handle: fused window + FFT + |X| (or complex) over many channels."""
+    """STFT handle: fused window + FFT + |X| (or complex) over many channels.
+
+    Frames 2j and 2j + 1 of a channel share one complex transform in the fused
+    kernels: a frame's rounding error is bounded relative to the larger frame
+    of its pair, and a NaN or Inf sample makes the frames that hold it
+    non-finite and may make their pair partners non-finite, and no other
+    frame.  The one-frame host API (vv_dsp_stft_process) has no pairs."""
 
     def __init__(self, nfft, hop, window=WIN_HANN):
         self.nfft, self.hop = nfft, hop
@@ -629,7 +635,13 @@ def unpack_half(half, nfft, out=None, stream=None):
 
 
 def hilbert(x, stream=None):
-    """x: (batch, N) or (N,) float32 device tensor -> complex64 analytic signal."""
+    """x: (batch, N) or (N,) float32 device tensor -> complex64 analytic signal.
+
+    For power-of-two N <= 8192 rows 2j and 2j + 1 of a batch share one complex
+    transform: a row's rounding error is bounded relative to the larger row of
+    its pair (2e-6 * max(1, log2 N) of the pair's max-abs), and a NaN or Inf
+    makes its own row non-finite and may make its pair partner non-finite, and
+    no other row.  Other N, and the one-row host API, have no pairs."""
     x2 = x if x.dim() == 2 else x.unsqueeze(0)
     b, n = x2.shape
     z = torch.empty((b, n), dtype=torch.complex64, device=x.device)
@@ -660,6 +672,17 @@ def instantaneous_frequency(phase, sample_rate, stream=None):
 
 
 def dct(x, dct_type=2, inverse=False, stream=None):
+    """x: (batch, N) or (N,) float32 device tensor -> its DCT rows (type 2, 3 or
+    4, forward or inverse; vv_dsp_dct_execute, dct.c:21-68, under the current
+    vv_dsp_set_nan_policy).
+
+    The forward type-2 transform of power-of-two N <= 8192 puts rows 2j and
+    2j + 1 of a batch into one complex transform: a row's rounding error is
+    bounded relative to the larger row of its pair (2e-6 * max(1, log2 N) of
+    the pair's max-abs), and under the PROPAGATE policy a NaN or Inf makes its
+    own row non-finite and may make its pair partner non-finite, and no other
+    row.  Every other type, direction and N, and the one-row host API, have
+    no pairs."""
     x2 = x if x.dim() == 2 else x.unsqueeze(0)
     b, n = x2.shape
     p = _vp()
