@@ -16,6 +16,7 @@
 #include "vv_dsp/filter/savgol.h"
 #include "vv_dsp/features/mel.h"
 #include "vv_dsp/features/pitch.h"
+#include "vv_dsp/features/pitch_track.h"
 #include "vv_dsp/features/spectral_shape.h"
 #include "vv_dsp/spectral/czt.h"
 #include "vv_dsp/spectral/phase_vocoder.h"
@@ -402,6 +403,35 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_pitch_frames_device(const vv_dsp_real* d_s
                                                           const vv_dsp_pitch_params* params,
                                                           const vv_dsp_pitch_out* out, size_t out_ch_stride,
                                                           size_t cmnd_ch_stride, void* stream);
+/* One f0 contour per channel from the YIN curves of its frames
+ * (vv_dsp/features/pitch_track.h, which states the path's definition, its
+ * numerics and the argument checks, made in its order before any device work).
+ * _pitch_track_: d_curves [nch][frames][row_stride] (row_stride >= tau_max + 1,
+ * channels cmnd_ch_stride floats apart: the cmnd plane of
+ * vv_dsp_pitch_frames_device) -> planes [nch][frames] (channels out_ch_stride
+ * values apart) and cost [nch]; vv_dsp_pitch_track_out: one pointer per output,
+ * NULL = not wanted.
+ * _pitch_track_frames_: d_signal [nch][n] -> the same planes, bit-identical to
+ * vv_dsp_pitch_frames_device (cmnd) followed by vv_dsp_pitch_track_device: the
+ * curves go to scratch in groups of channels, at most 2 GiB of curves a group
+ * (at least one channel), and no value depends on the grouping.  track->tau_max
+ * must not exceed the curves' last lag (vv_dsp_pitch_lag_range's tau_max), else
+ * INVALID_SIZE; vv_dsp_pitch_track_params_default gives matching parameters.
+ * The tracker's own scratch is one byte per state and frame plus four bytes per
+ * frame, in channel groups of at most 4 GiB.
+ * vvhip_debug_get("STAT_PITCH_TRACK") counts the tracker's launches. */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_pitch_track_device(const vv_dsp_real* d_curves, size_t frames, size_t nch,
+                                                         size_t row_stride, size_t cmnd_ch_stride,
+                                                         const vv_dsp_pitch_track_params* params,
+                                                         const vv_dsp_pitch_track_out* out, size_t out_ch_stride,
+                                                         void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_pitch_track_frames_device(const vv_dsp_real* d_signal, size_t n, size_t nch,
+                                                                size_t ch_stride, size_t frame_len, size_t hop_len,
+                                                                int center, const vv_dsp_real* d_window,
+                                                                const vv_dsp_pitch_params* pitch,
+                                                                const vv_dsp_pitch_track_params* track,
+                                                                const vv_dsp_pitch_track_out* out,
+                                                                size_t out_ch_stride, void* stream);
 /* Per-frame spectral shape descriptors of power rows
  * (vv_dsp/features/spectral_shape.h, which states every value's definition, its
  * numerics and the argument checks, made in its order before any device work).

@@ -72,7 +72,8 @@ const char* vvhip_last_error(void);
  *       "STAT_LPC_WAVE", "STAT_LPC_GENERIC", "STAT_IIR_EXACT",
  *       "STAT_IIR_CHUNKED", "STAT_STATS_WAVE", "STAT_STATS_LONG",
  *       "STAT_INTERP_ONE", "STAT_INTERP_ROWS", "STAT_PITCH_WAVE",
- *       "STAT_PVOC_ROWS": launches of that path since the last clear);
+ *       "STAT_PVOC_ROWS", "STAT_PITCH_TRACK": launches of that path since the
+ *       last clear);
  *       -2 unknown.
  * The environment is read once per process, and only with VVHIP_AB=1 set. */
 int vvhip_debug_set(const char* name, long long value);
@@ -420,6 +421,43 @@ int vvhip_pitch_frames_device(const float* d_signal, size_t n, size_t nch, size_
                               const vvhip_pitch_params* params, const vvhip_pitch_out* out, size_t out_ch_stride,
                               size_t cmnd_ch_stride, void* stream);
 int vvhip_pitch_host(const float* x, size_t n, const vvhip_pitch_params* params, float* f0, float* aperiodicity);
+
+/* ---- f0 tracking over the YIN curves (include/vv_dsp/features/pitch_track.h:
+ * the definition and the checks, made in its order before any device work) ----
+ * vvhip_pitch_track_params / vvhip_pitch_track_out: the layouts of
+ * vv_dsp_pitch_track_params and vv_dsp_pitch_track_out.  _params_default: host
+ * arithmetic over vvhip_pitch_lag_range.  _track_: curves [nch][frames][row_stride]
+ * (channels cmnd_ch_stride floats apart) -> planes [nch][frames] (channels
+ * out_ch_stride values apart) and cost [nch].  _track_frames_: signal [nch][n] ->
+ * the same planes: vvhip_pitch_frames_device into scratch curves, then the
+ * tracker, in channel groups of at most 2 GiB of curves (at least one channel);
+ * track->tau_max must not exceed the curves' last lag.  The tracker's own scratch
+ * is one byte per state and frame, in channel groups of at most 4 GiB.  Knob
+ * PTRACK_GROUP = g > 0 forces groups of g channels; no value depends on it.
+ * "STAT_PITCH_TRACK" counts the tracker's launches (pitch_track_kernels.hip).
+ * _host: one channel of curves in host memory. */
+typedef struct vvhip_pitch_track_params {
+    float sample_rate;
+    uint32_t tau_min, tau_max;
+    float lambda, jump_cost, switch_cost, unvoiced_cost;
+    uint32_t max_step;
+} vvhip_pitch_track_params;
+typedef struct vvhip_pitch_track_out {
+    uint32_t* lag;
+    float *f0, *aperiodicity;
+    double* cost;
+} vvhip_pitch_track_out;
+int vvhip_pitch_track_params_default(const vvhip_pitch_params* pitch, size_t frame_len,
+                                     vvhip_pitch_track_params* track);
+int vvhip_pitch_track_device(const float* d_curves, size_t frames, size_t nch, size_t row_stride,
+                             size_t cmnd_ch_stride, const vvhip_pitch_track_params* params,
+                             const vvhip_pitch_track_out* out, size_t out_ch_stride, void* stream);
+int vvhip_pitch_track_frames_device(const float* d_signal, size_t n, size_t nch, size_t ch_stride, size_t frame_len,
+                                    size_t hop, size_t frames, int center, const float* d_window,
+                                    const vvhip_pitch_params* pitch, const vvhip_pitch_track_params* track,
+                                    const vvhip_pitch_track_out* out, size_t out_ch_stride, void* stream);
+int vvhip_pitch_track_host(const float* curves, size_t frames, size_t row_stride,
+                           const vvhip_pitch_track_params* params, const vvhip_pitch_track_out* out);
 
 /* ---- Per-frame spectral shape (include/vv_dsp/features/spectral_shape.h: the
  * definitions and the checks, made in its order before any device work) ----

@@ -18,11 +18,11 @@ enum Knob : int {
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
-    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_SHAPE_DWORD, KNOB_PVOC_GROUP, KNOB_PVOC_PLANE, KNOB_COUNT
+    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_SHAPE_DWORD, KNOB_PVOC_GROUP, KNOB_PVOC_PLANE, KNOB_PTRACK_GROUP, KNOB_COUNT
 };
 long long knob(Knob k, long long dflt);
 // launches of the paths the tests must see taken (vvhip_debug_get("STAT_..."))
-enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_PITCH_WAVE, STAT_SHAPE_WAVE, STAT_SHAPE_VEC16, STAT_PVOC_ROWS, STAT_COUNT };
+enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_PITCH_WAVE, STAT_SHAPE_WAVE, STAT_SHAPE_VEC16, STAT_PVOC_ROWS, STAT_PITCH_TRACK, STAT_COUNT };
 void stat_inc(Stat s);
 
 // Device-resident W_N^k = exp(-2*pi*i*k/N) table, k < N, f32 rounded from double.
@@ -404,6 +404,42 @@ struct PitchOut {
 // The row sits in LDS as f64 where four rows fit 64 KiB, as f32 beyond or with
 // f32_rows (knob PITCH_F32 = 1): the conversion is exact, the bits are the same.
 hipError_t launch_pitch(const FrameSrc& src, const PitchCfg& cfg, const PitchOut& out, bool f32_rows, hipStream_t s);
+
+// ---- f0 tracking over the YIN curves (pitch_track_kernels.hip), include/vv_dsp/features/pitch_track.h ----
+constexpr int PTRACK_MAX_STEP = 126;             // VV_DSP_PITCH_TRACK_MAX_STEP: a predecessor code is one byte
+constexpr int PTRACK_MAX_STATES = 4096;          // VV_DSP_PITCH_TRACK_MAX_STATES
+constexpr int PTRACK_BLOCK = 64;                 // L: frames of predecessor rows the backtrace stages at most
+struct PtrackCfg {
+    double sample_rate = 0.0, lambda = 0.0, jump = 0.0, sw = 0.0, uc = 0.0;
+    int tau_min = 0, tau_max = 0, B = 0;
+    int S() const { return tau_max - tau_min + 1; }
+};
+// curves [nch][F][row_stride] (channels cmnd_ch_stride floats apart) -> planes [nch][F]
+// (channels ch_stride values apart), cost [nch]; null: not wanted
+struct PtrackArgs {
+    const float* q = nullptr;
+    long long nch = 0, F = 0, row_stride = 0, cmnd_ch_stride = 0, ch_stride = 0;
+    unsigned* lag = nullptr;
+    float* f0 = nullptr;
+    float* aperiodicity = nullptr;
+    double* cost = nullptr;
+    // scratch of ptrack_scratch_bytes(): per channel F rows of predecessor bytes, F best
+    // lags, the end state
+    unsigned char* work = nullptr;
+};
+// bytes of a predecessor row: S voiced states and U, rounded up to 16
+constexpr size_t ptrack_row_bytes(int S) { return ((size_t)S + 1 + 15) / 16 * 16; }
+inline size_t ptrack_scratch_bytes(int S, long long nch, long long F) {
+    return (size_t)nch * ((size_t)F * (ptrack_row_bytes(S) + 4) + 16);
+}
+// frames per staged block of the backtrace: PTRACK_BLOCK where that many rows fit 60 KiB
+constexpr int ptrack_block(int S) {
+    return (int)((60u << 10) / ptrack_row_bytes(S)) < PTRACK_BLOCK ? (int)((60u << 10) / ptrack_row_bytes(S))
+                                                                    : PTRACK_BLOCK;
+}
+// forward pass (one wave per channel up to 64 states, one workgroup beyond) and
+// backtrace on stream s; nch > 0, F > 0, checked sizes
+hipError_t launch_pitch_track(const PtrackCfg& cfg, const PtrackArgs& a, hipStream_t s);
 
 // ---- per-frame spectral shape (shape_kernels.hip), include/vv_dsp/features/spectral_shape.h ----
 constexpr int SHAPE_MAX_BINS = 8193;             // K = n_fft / 2 + 1 of a row

@@ -54,6 +54,21 @@ class PitchOut(C.Structure):
 PITCH_NAMES = tuple(name for name, _ in PitchOut._fields_)
 
 
+class PitchTrackParams(C.Structure):
+    """vv_dsp_pitch_track_params (vv_dsp/features/pitch_track.h)"""
+    _fields_ = [("sample_rate", C.c_float), ("tau_min", C.c_uint32), ("tau_max", C.c_uint32), ("lambda_", C.c_float),
+                ("jump_cost", C.c_float), ("switch_cost", C.c_float), ("unvoiced_cost", C.c_float),
+                ("max_step", C.c_uint32)]
+
+
+class PitchTrackOut(C.Structure):
+    """vv_dsp_pitch_track_out: one device pointer per output, NULL = not wanted"""
+    _fields_ = [(name, C.c_void_p) for name in ("lag", "f0", "aperiodicity", "cost")]
+
+
+TRACK_NAMES = tuple(name for name, _ in PitchTrackOut._fields_)
+
+
 class SpectralShapeParams(C.Structure):
     """vv_dsp_spectral_shape_params (vv_dsp/features/spectral_shape.h)"""
     _fields_ = [("n_fft", C.c_size_t), ("sample_rate", C.c_float), ("magnitude", C.c_int), ("k_min", C.c_size_t),
@@ -170,6 +185,12 @@ def lib():
     L.vv_dsp_pitch_device.argtypes = [_vp, _sz, _sz, _sz, C.POINTER(PitchParams), C.POINTER(PitchOut), _sz, _vp]
     L.vv_dsp_pitch_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, C.POINTER(PitchParams),
                                              C.POINTER(PitchOut), _sz, _sz, _vp]
+    L.vv_dsp_pitch_track_params_default.argtypes = [C.POINTER(PitchParams), _sz, C.POINTER(PitchTrackParams)]
+    L.vv_dsp_pitch_track.argtypes = [_vp, _sz, _sz, C.POINTER(PitchTrackParams), C.POINTER(PitchTrackOut)]
+    L.vv_dsp_pitch_track_device.argtypes = [_vp, _sz, _sz, _sz, _sz, C.POINTER(PitchTrackParams),
+                                            C.POINTER(PitchTrackOut), _sz, _vp]
+    L.vv_dsp_pitch_track_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, C.POINTER(PitchParams),
+                                                   C.POINTER(PitchTrackParams), C.POINTER(PitchTrackOut), _sz, _vp]
     L.vv_dsp_spectral_shape.argtypes = [_vp, _vp, C.POINTER(SpectralShapeParams), _vp]
     L.vv_dsp_spectral_shape_device.argtypes = [_vp, _sz, _sz, _sz, C.POINTER(SpectralShapeParams),
                                                C.POINTER(SpectralShapeOut), _vp]
@@ -968,6 +989,80 @@ def pitch_frames(sig, frame_len, hop, params, what, window=None, center=False, s
                                                 int(bool(center)), win,
                                                 C.byref(params), C.byref(out), fr, fr * (tau_max + 1),
                                                 _stream(stream)), "pitch_frames_device")
+    return _planes_of(planes, sig)
+
+
+def pitch_track_params(params, frame_len):
+    """the tracker's default parameters for the curves of `params` on frames of frame_len
+    samples (vv_dsp_pitch_track_params_default; host arithmetic, needs no device)"""
+    if not isinstance(params, PitchParams):
+        raise VvError("pitch_track: params must be a PitchParams")
+    tp = PitchTrackParams()
+    _check(lib().vv_dsp_pitch_track_params_default(C.byref(params), frame_len, C.byref(tp)),
+           "pitch_track_params_default")
+    return tp
+
+
+def _track_planes(tparams, what, nch, frames, device, who):
+    """the output tensors of `what` and the vv_dsp_pitch_track_out that points at them"""
+    if not isinstance(tparams, PitchTrackParams):
+        raise VvError(f"{who}: track parameters must be a PitchTrackParams")
+    if isinstance(what, str):
+        what = (what,)
+    planes, out = {}, PitchTrackOut()
+    for name in what:
+        if name not in TRACK_NAMES:
+            raise VvError(f"{who}: unknown output {name!r} (one of {', '.join(TRACK_NAMES)})")
+        if name not in planes:
+            if name == "cost":
+                planes[name] = torch.empty((nch,), dtype=torch.float64, device=device)
+            else:
+                planes[name] = torch.empty((nch, frames), dtype=torch.int32 if name == "lag" else torch.float32,
+                                           device=device)
+            setattr(out, name, planes[name].data_ptr())
+    return planes, out
+
+
+def pitch_track(curves, tparams, what, stream=None):
+    """One f0 contour per channel from its YIN curves (vv_dsp/features/pitch_track.h):
+    curves (frames, w) or (nch, frames, w) float32 device rows, w >= tau_max + 1 (the cmnd
+    output of pitch_frames; rows curves.stride(-2) and channels curves.stride(0) floats
+    apart) -> {name: tensor} for the names in `what` (TRACK_NAMES): lag (nch, frames)
+    int32 (0 = unvoiced), f0, aperiodicity (nch, frames), cost (nch,) float64."""
+    c3 = curves if curves.dim() == 3 else curves.unsqueeze(0)
+    if curves.dim() not in (2, 3) or c3.dtype != torch.float32 or not c3.is_cuda or \
+            (c3.shape[2] > 1 and c3.stride(2) != 1):
+        raise VvError("pitch_track: float32 device curves (frames, w) or (nch, frames, w) with unit lag stride")
+    nch, fr, w = c3.shape
+    row = c3.stride(1) if fr > 1 else w
+    chs = c3.stride(0) if nch > 1 else fr * row
+    if row < w or (nch > 1 and chs < (fr - 1) * row + w):
+        raise VvError("pitch_track: overlapping rows or channels")
+    planes, out = _track_planes(tparams, what, nch, fr, curves.device, "pitch_track")
+    if w < tparams.tau_max + 1:
+        raise VvError(f"pitch_track: curves of {w} values, tau_max {tparams.tau_max}")
+    if planes and fr and nch:
+        _check(lib().vv_dsp_pitch_track_device(_vp(c3.data_ptr()), fr, nch, row, chs, C.byref(tparams), C.byref(out),
+                                               fr, _stream(stream)), "pitch_track_device")
+    return planes if curves.dim() == 3 else {k: v[0] for k, v in planes.items()}
+
+
+def pitch_track_frames(sig, frame_len, hop, params, tparams, what, window=None, center=False, stream=None):
+    """Signal (nch, n) or (n,) float32 -> the tracked planes of pitch_track(): pitch_frames
+    (cmnd) into scratch curves and the tracker, in channel groups, bit-identical to the
+    two calls (vv_dsp_pitch_track_frames_device)."""
+    sig2, nch, n = _signal(sig, "pitch_track_frames")
+    if frame_len <= 0 or hop <= 0:
+        raise VvError(f"pitch_track_frames: frame_len {frame_len}, hop {hop}")
+    if not isinstance(params, PitchParams):
+        raise VvError("pitch_track_frames: params must be a PitchParams")
+    win = _window(window, frame_len, "pitch_track_frames")
+    fr = num_frames(n, frame_len, hop, center)
+    planes, out = _track_planes(tparams, what, nch, fr, sig.device, "pitch_track_frames")
+    if planes and fr and nch:
+        _check(lib().vv_dsp_pitch_track_frames_device(_vp(sig2.data_ptr()), n, nch, sig2.stride(0), frame_len, hop,
+                                                      int(bool(center)), win, C.byref(params), C.byref(tparams),
+                                                      C.byref(out), fr, _stream(stream)), "pitch_track_frames_device")
     return _planes_of(planes, sig)
 
 
