@@ -6,6 +6,7 @@
 #include "vv_dsp/filter/fir.h"
 #include "vv_dsp/filter/iir.h"
 #include "vv_dsp/filter/savgol.h"
+#include "vv_dsp/filter/median.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -18,4 +18,5 @@ int vv_dsp_spectral_dummy(void);
 #include "vv_dsp/spectral/czt.h"
 #include "vv_dsp/spectral/hilbert.h"
 #include "vv_dsp/spectral/phase_vocoder.h"
+#include "vv_dsp/spectral/hpss.h"
 #endif

@@ -14,12 +14,14 @@
 #include "vv_dsp/filter/fir.h"
 #include "vv_dsp/filter/iir.h"
 #include "vv_dsp/filter/savgol.h"
+#include "vv_dsp/filter/median.h"
 #include "vv_dsp/features/mel.h"
 #include "vv_dsp/features/pitch.h"
 #include "vv_dsp/features/pitch_track.h"
 #include "vv_dsp/features/spectral_shape.h"
 #include "vv_dsp/spectral/czt.h"
 #include "vv_dsp/spectral/phase_vocoder.h"
+#include "vv_dsp/spectral/hpss.h"
 #include "vv_dsp/envelope/cepstrum.h"
 #include "vv_dsp/envelope/minphase.h"
 #include "vv_dsp/envelope/lpc.h"
@@ -515,6 +517,54 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_stft_time_stretch_device(vv_dsp_stft* h, c
                                                                size_t nch, size_t ch_stride, double rate,
                                                                vv_dsp_real* d_out, size_t out_ch_stride, void* stream,
                                                                size_t* out_len);
+/* Running median of `batch` rows of n samples, x_stride / y_stride floats apart
+ * (vv_dsp/filter/median.h, which states the order, the boundary modes and the
+ * argument checks, made in its order before any device work).  One launch, 256
+ * positions of a row per block: the tile and its halo are turned into keys in
+ * LDS with the boundary mode resolved, then every lane selects rank h of its
+ * window by counting (window_length < 33) or bit by bit (knob MEDIAN_SELECT = 1 /
+ * 2 forces either, with the same bits).  The floats between n and a stride are
+ * never read or written; a row's output never depends on the batch, the strides
+ * or the entry point.  d_y must not overlap d_x (not checked).  batch == 0: OK. */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_medfilt_device(const vv_dsp_real* d_x, size_t n, size_t batch, size_t x_stride,
+                                                     int window_length, vv_dsp_medfilt_mode mode, vv_dsp_real* d_y,
+                                                     size_t y_stride, void* stream);
+/* Harmonic-percussive separation (vv_dsp/spectral/hpss.h, which states every
+ * value's definition and the argument checks, made in its order before any
+ * device work).
+ * _hpss_: `rows` rows of n_fft/2 + 1 powers, row_pitch floats apart, in groups of
+ * rows_per_group rows (0: one group; the last may be short) -> the planes of
+ * `out` that are not NULL, [rows][out_pitch], the pads past bin n_fft/2 neither
+ * read nor written.  Launches: the time median (reads the rows, writes H) when
+ * harm or a mask is wanted; the frequency median (reads the rows, and H where a
+ * mask is wanted; writes perc and the masks that are wanted) when perc or a mask
+ * is wanted.  Scratch, allocated and freed on the stream: 4 rows (n_fft/2 + 1)
+ * bytes for H when a mask is wanted and harm is not, else none.
+ * _stft_hpss_: d_signal [nch][n] (ch_stride floats apart) -> d_out_harm and
+ * d_out_perc [nch][out_len] (out_ch_stride floats apart; either may be NULL),
+ * out_len = (T - 1) hop + fft_size with T the handle's frame count of n samples
+ * (a signal shorter than one frame is one zero-padded frame, as everywhere in the
+ * STFT): vv_dsp_stft_power_device rows; vv_dsp_hpss_device masks, one group per
+ * channel; vv_dsp_stft_spectrum_device rows whose bin k has its real and its
+ * imaginary part each multiplied in float by mask[k] (bin n_fft - k by the same
+ * mask); vv_dsp_stft_reconstruct_device of each channel's rows into zeroed out and
+ * norm; y[i] = norm[i] > VV_DSP_PVOC_NORM_FLOOR ? out[i] / norm[i] : 0 -- the
+ * values of the public calls in sequence, bit for bit.  The rows live in
+ * stream-ordered scratch, a group of channels at a time (as many as fit 1 GiB, at
+ * least one; knob HPSS_GROUP = k: k channels per group; the result does not depend
+ * on it).  Checks in this order, as vv_dsp_stft_time_stretch_device orders its
+ * own: NULL handle, params or signal, or both outputs NULL; fft_size < 2,
+ * params->n_fft != fft_size, ch_stride < n (for nch > 1 only) or out_ch_stride <
+ * out_len (for one channel too) -- INVALID_SIZE; then checks 3 and 4 of hpss.h.
+ * *out_len (may be NULL) is set once every check has passed; nch == 0: OK. */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_hpss_device(const vv_dsp_real* d_power, size_t rows, size_t row_pitch,
+                                                  size_t rows_per_group, const vv_dsp_hpss_params* params,
+                                                  const vv_dsp_hpss_out* out, size_t out_pitch, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_stft_hpss_device(vv_dsp_stft* h, const vv_dsp_hpss_params* params,
+                                                       const vv_dsp_real* d_signal, size_t n, size_t nch,
+                                                       size_t ch_stride, vv_dsp_real* d_out_harm,
+                                                       vv_dsp_real* d_out_perc, size_t out_ch_stride, void* stream,
+                                                       size_t* out_len);
 /* Biquad cascade on `batch` rows of n samples, x_stride / y_stride floats apart
  * (vv_dsp/filter/iir.h, iir.c:21-43).  d_coef [num_stages][5] = b0 b1 b2 a1 a2
  * per stage, one cascade for every row.  d_state [batch][num_stages][2] = z1 z2

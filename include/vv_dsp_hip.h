@@ -36,6 +36,8 @@
  *                  include/vv_dsp/features/spectral_shape.h defines them
  *   vvhip_pvoc_* / _stft_stretch_*: no reference source;
  *                  include/vv_dsp/spectral/phase_vocoder.h defines them
+ *   vvhip_medfilt_* / _hpss_* / _stft_hpss_*: no reference source;
+ *                  include/vv_dsp/filter/median.h and spectral/hpss.h define them
  */
 #ifndef VV_DSP_HIP_H
 #define VV_DSP_HIP_H
@@ -514,6 +516,35 @@ int vvhip_pvoc_host(const float* spec, size_t T, size_t n_fft, double start, dou
 int vvhip_stft_stretch_length(size_t n, size_t nfft, size_t hop, double rate, size_t* rows, size_t* out_len);
 int vvhip_stft_stretch_device(vvhip_stft* h, const float* d_signal, size_t n, size_t nch, size_t ch_stride,
                               double rate, float* d_out, size_t out_ch_stride, void* stream, size_t* out_len);
+
+/* ---- Running median and HPSS (include/vv_dsp/filter/median.h and
+ * include/vv_dsp/spectral/hpss.h: the definitions and the checks, made in their
+ * order before any device work; median_kernels.hip) ----
+ * _medfilt_: `batch` rows of n floats, strides in floats; _host: one row in host
+ * memory.  Knob MEDIAN_SELECT = 1 / 2 forces the counting / the bitwise select
+ * (same bits).  vvhip_hpss_params / vvhip_hpss_out: the layouts of
+ * vv_dsp_hpss_params and _out.  _hpss_: power rows -> the planes that are
+ * wanted; _hpss_host: one group of packed rows in host memory.  _stft_hpss_:
+ * signal [nch][n] -> the harmonic and the percussive signal [nch][out_len], in
+ * channel groups (knob HPSS_GROUP = k: k channels per group). */
+typedef struct vvhip_hpss_params {
+    size_t n_fft;
+    int magnitude, win_harm, win_perc;
+    float margin_harm, margin_perc;
+    int mask;
+} vvhip_hpss_params;
+typedef struct vvhip_hpss_out {
+    float *harm, *perc, *mask_harm, *mask_perc;
+} vvhip_hpss_out;
+int vvhip_medfilt_device(const float* d_x, size_t n, size_t batch, size_t x_stride, int window_length, int mode,
+                         float* d_y, size_t y_stride, void* stream);
+int vvhip_medfilt_host(const float* x, size_t n, int window_length, int mode, float* y);
+int vvhip_hpss_device(const float* d_power, size_t rows, size_t row_pitch, size_t rows_per_group,
+                      const vvhip_hpss_params* params, const vvhip_hpss_out* out, size_t out_pitch, void* stream);
+int vvhip_hpss_host(const float* power_rows, size_t rows, const vvhip_hpss_params* params, const vvhip_hpss_out* out);
+int vvhip_stft_hpss_device(vvhip_stft* h, const vvhip_hpss_params* params, const float* d_signal, size_t n, size_t nch,
+                           size_t ch_stride, float* d_out_harm, float* d_out_perc, size_t out_ch_stride,
+                           void* stream, size_t* out_len);
 
 /* ---- Spectral utilities (src/spectral/utils.c:5-73) ----
  * `batch` contiguous rows of n: fftshift (inverse 0) / ifftshift (inverse 1) of

@@ -18,7 +18,7 @@ enum Knob : int {
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
-    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_SHAPE_DWORD, KNOB_PVOC_GROUP, KNOB_PVOC_PLANE, KNOB_PTRACK_GROUP, KNOB_COUNT
+    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_SHAPE_DWORD, KNOB_PVOC_GROUP, KNOB_PVOC_PLANE, KNOB_PTRACK_GROUP, KNOB_MEDIAN_SELECT, KNOB_HPSS_GROUP, KNOB_COUNT
 };
 long long knob(Knob k, long long dflt);
 // launches of the paths the tests must see taken (vvhip_debug_get("STAT_..."))
@@ -503,6 +503,41 @@ hipError_t launch_pvoc(const PvocArgs& a, hipStream_t s);
 // y[c][i] = norm[c][i] > PVOC_NORM_FLOOR ? y[c][i] / norm[c][i] : 0 for i < len (norm rows contiguous)
 hipError_t launch_pvoc_normalize(float* y, long long y_stride, const float* norm, long long len, long long nch,
                                  hipStream_t s);
+
+// ---- running median and HPSS (median_kernels.hip), include/vv_dsp/filter/median.h,
+// include/vv_dsp/spectral/hpss.h ----
+constexpr int MED_MAX_WINDOW = 127;               // VV_DSP_MEDFILT_MAX_WINDOW
+constexpr int MED_TILE = 256;                     // positions of a line per block (row direction)
+constexpr int MED_RUN = 64;                       // rows of a group per block (column direction)
+constexpr int MED_RADIX_FROM = 33;                // windows from here on: the bitwise select
+constexpr int HPSS_MAX_BINS = 8193;               // VV_DSP_HPSS_MAX_BINS
+enum MedMode : int { MED_REFLECT, MED_NEAREST, MED_ZERO };
+enum HpssMask : int { HPSS_HARD, HPSS_SOFT, HPSS_WIENER };
+// One launch of either direction.  Values x[line * x_pitch + i], i < n, lines in
+// groups of rpg (> 0) consecutive lines; sqrt_w: the value is sqrtf(x).  Row
+// direction: the window runs along i.  Column direction: along the lines of a group.
+struct MedArgs {
+    const float* x = nullptr;
+    long long lines = 0, n = 0, x_pitch = 0, rpg = 0;
+    int L = 1, mode = MED_REFLECT, sqrt_w = 0, radix = 0;
+    float* y = nullptr;            // the medians [line * y_pitch + i], or null (row direction with masks)
+    long long y_pitch = 0;
+    // row direction with masks: the other median H [line * h_pitch + i] is read and the
+    // masks that are wanted are written at y_pitch
+    const float* H = nullptr;
+    long long h_pitch = 0;
+    float *mask_h = nullptr, *mask_p = nullptr;
+    double margin_h = 1.0, margin_p = 1.0;
+    int mask = HPSS_HARD;
+};
+// whether one launch takes these counts (flat grids below 2^31 blocks)
+bool med_rows_supported(long long lines, long long n);
+bool med_cols_supported(long long lines, long long n, long long rpg);
+hipError_t launch_med_rows(const MedArgs& a, hipStream_t s);
+hipError_t launch_med_cols(const MedArgs& a, hipStream_t s);
+// spec rows [rows][n_fft] float pairs times mask [rows][K] (bin j >= K by mask[n_fft - j]) -> out
+hipError_t launch_hpss_apply(const float2* spec, const float* mask, float2* out, long long rows, long long n_fft,
+                             hipStream_t s);
 
 // ---- biquad cascade (iir_kernels.hip), src/filter/iir.c:21-43 -----------------
 constexpr int IIR_MAX_STAGES = 8;        // stages one walk holds in registers; longer cascades run in groups

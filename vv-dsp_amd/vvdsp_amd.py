@@ -83,6 +83,23 @@ class SpectralShapeOut(C.Structure):
 
 SHAPE_NAMES = tuple(name for name, _ in SpectralShapeOut._fields_)
 
+MEDFILT_REFLECT, MEDFILT_NEAREST, MEDFILT_ZERO = 0, 1, 2
+HPSS_HARD, HPSS_SOFT, HPSS_WIENER = 0, 1, 2
+
+
+class HpssParams(C.Structure):
+    """vv_dsp_hpss_params (vv_dsp/spectral/hpss.h)"""
+    _fields_ = [("n_fft", C.c_size_t), ("magnitude", C.c_int), ("win_harm", C.c_int), ("win_perc", C.c_int),
+                ("margin_harm", C.c_float), ("margin_perc", C.c_float), ("mask", C.c_int)]
+
+
+class HpssOut(C.Structure):
+    """vv_dsp_hpss_out: one device pointer per plane, NULL = not wanted"""
+    _fields_ = [(name, C.c_void_p) for name in ("harm", "perc", "mask_harm", "mask_perc")]
+
+
+HPSS_NAMES = tuple(name for name, _ in HpssOut._fields_)
+
 
 class VvError(RuntimeError):
     pass
@@ -203,7 +220,13 @@ def lib():
     L.vv_dsp_stft_time_stretch_length.argtypes = [_vp, _sz, C.c_double, C.POINTER(_sz), C.POINTER(_sz)]
     L.vv_dsp_stft_time_stretch_device.argtypes = [_vp, _vp, _sz, _sz, _sz, C.c_double, _vp, _sz, _vp, C.POINTER(_sz)]
     L.vvhip_stft_stretch_length.argtypes = [_sz, _sz, _sz, C.c_double, C.POINTER(_sz), C.POINTER(_sz)]
-    L.vv_dsp_iir_apply_device.argtypes = [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]
+    L.vv_dsp_medfilt.argtypes = [_vp, _sz, C.c_int, C.c_int, _vp]
+    L.vv_dsp_medfilt_device.argtypes = [_vp, _sz, _sz, _sz, C.c_int, C.c_int, _vp, _sz, _vp]
+    L.vv_dsp_hpss.argtypes = [_vp, _sz, C.POINTER(HpssParams), C.POINTER(HpssOut)]
+    L.vv_dsp_hpss_device.argtypes = [_vp, _sz, _sz, _sz, C.POINTER(HpssParams), C.POINTER(HpssOut), _sz, _vp]
+    L.vv_dsp_stft_hpss_device.argtypes = [_vp, C.POINTER(HpssParams), _vp, _sz, _sz, _sz, _vp, _vp, _sz, _vp,
+                                          C.POINTER(_sz)]
+    L.vv_dsp_iir_apply_device.argtypes =[_vp, _sz, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]
     L.vv_dsp_savgol_coeffs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, _vp]
     L.vv_dsp_savgol_device.argtypes = [_vp, _sz, _sz, _sz, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp, _sz,
                                        _vp]
@@ -423,6 +446,28 @@ class Stft:
                                                          C.byref(got)), "stft_time_stretch_device")
             assert got.value == ln
         return out
+
+    def hpss(self, sig, params, harm=True, perc=True, stream=None):
+        """sig: (nch, n) or (n,) float32 -> (harmonic, percussive), each (nch, out_len) or
+        (out_len,), out_len = (frames - 1) * hop + nfft, or None where not asked for:
+        power() -> hpss() masks -> spectrogram(complex_out=True) times a mask ->
+        reconstruct() into zeros -> out / norm, in one call with the rows in stream-ordered
+        scratch (vv_dsp_stft_hpss_device), bit-identical to those steps."""
+        if not isinstance(params, HpssParams):
+            raise VvError("stft hpss: params must be an HpssParams")
+        if not (harm or perc):
+            raise VvError("stft hpss: neither output asked for")
+        sig2, nch, n = _signal(sig, "stft hpss")
+        ln = (self.frames(n) - 1) * self.hop + self.nfft
+        outs = [torch.empty((nch, ln), dtype=torch.float32, device=sig.device) if want else None
+                for want in (harm, perc)]
+        got = _sz(0)
+        if nch:
+            _check(lib().vv_dsp_stft_hpss_device(self.h, C.byref(params), _vp(sig2.data_ptr()), n, nch, sig2.stride(0),
+                                                 *(None if o is None else _vp(o.data_ptr()) for o in outs), ln,
+                                                 _stream(stream), C.byref(got)), "stft_hpss_device")
+            assert got.value == ln
+        return tuple(o if o is None or sig.dim() == 2 else o[0] for o in outs)
 
     def frames_range(self, sig, frame0, nframes, kind=0, out=None, stream=None):
         """Rows of frames [frame0, frame0 + nframes) of sig's spectrogram (one shard
@@ -1268,6 +1313,61 @@ def savgol(x, window_length, polyorder, deriv=0, delta=1.0, mode=0, out=None, st
                                       deriv, delta, int(mode), _vp(y2.data_ptr()), y2.stride(0) if b > 1 else n,
                                       _stream(stream)), "savgol_device")
     return y if out is not None or x.dim() == 2 else y[0]
+
+
+def medfilt(x, window_length, mode=0, out=None, stream=None):
+    """Running median of float32 rows (vv_dsp/filter/median.h): x (..., n) -> (..., n),
+    y[i] the value of rank window_length // 2 of x[i - h .. i + h] in the order
+    -inf < .. < -0 < +0 < .. < +inf < NaN, bit for bit one of its inputs.  mode: 0
+    reflect, 1 nearest, 2 zero (MEDFILT_*).  out must not overlap x."""
+    x2 = _strided_rows(x, "medfilt input")
+    b, n = x2.shape
+    y = torch.empty((b, n), dtype=torch.float32, device=x.device) if out is None else out
+    y2 = _strided_rows(y, "medfilt output")
+    if tuple(y2.shape) != (b, n):
+        raise VvError(f"medfilt output: shape {tuple(y2.shape)}, expected {(b, n)}")
+    _check(lib().vv_dsp_medfilt_device(_vp(x2.data_ptr()), n, b, x2.stride(0) if b > 1 else n, int(window_length),
+                                       int(mode), _vp(y2.data_ptr()), y2.stride(0) if b > 1 else n, _stream(stream)),
+           "medfilt_device")
+    return y if out is not None or x.dim() == 2 else y[0]
+
+
+def hpss(power, params, what, rows_per_group=0, stream=None):
+    """Harmonic-percussive separation of float32 device power rows
+    (vv_dsp/spectral/hpss.h): power (rows, pitch) or (ch, frames, pitch), the rows
+    power.stride(-2) >= n_fft//2 + 1 floats apart (bins 0..n_fft//2 of each are read) ->
+    {name: tensor (rows, n_fft//2 + 1) or (ch, frames, n_fft//2 + 1)} for the names in
+    `what` (HPSS_NAMES: harm, perc, mask_harm, mask_perc).  A (ch, frames, pitch) tensor is
+    ch groups of `frames` rows; for (rows, pitch), rows_per_group rows form a group (0: one)."""
+    if not isinstance(params, HpssParams):
+        raise VvError("hpss: params must be an HpssParams")
+    if power.dim() not in (2, 3) or power.dtype != torch.float32 or not power.is_cuda:
+        raise VvError("hpss: float32 device rows (rows, pitch) or (ch, frames, pitch)")
+    nb = params.n_fft // 2 + 1
+    lead = tuple(power.shape[:-1])
+    rows = 1
+    for d in lead:
+        rows *= d
+    pitch = power.stride(-2) if power.shape[-2] > 1 else power.shape[-1]
+    if power.shape[-1] < nb or (power.shape[-1] > 1 and power.stride(-1) != 1) or pitch < nb:
+        raise VvError(f"hpss: rows of {power.shape[-1]} floats, pitch {pitch}, for {nb} bins")
+    if power.dim() == 3:
+        if power.shape[0] > 1 and power.stride(0) != power.shape[1] * pitch:
+            raise VvError("hpss: channels must follow each other, frames x pitch floats apart")
+        rows_per_group = power.shape[1]
+    if isinstance(what, str):
+        what = (what,)
+    planes, out = {}, HpssOut()
+    for name in what:
+        if name not in HPSS_NAMES:
+            raise VvError(f"hpss: unknown output {name!r} (one of {', '.join(HPSS_NAMES)})")
+        if name not in planes:
+            planes[name] = torch.empty(lead + (nb,), dtype=torch.float32, device=power.device)
+            setattr(out, name, planes[name].data_ptr())
+    if planes and rows:
+        _check(lib().vv_dsp_hpss_device(_vp(power.data_ptr()), rows, pitch, rows_per_group, C.byref(params),
+                                        C.byref(out), nb, _stream(stream)), "hpss_device")
+    return planes
 
 
 INTERP_LINEAR, INTERP_CUBIC = 0, 1
