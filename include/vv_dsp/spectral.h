@@ -19,4 +19,5 @@ int vv_dsp_spectral_dummy(void);
 #include "vv_dsp/spectral/hilbert.h"
 #include "vv_dsp/spectral/phase_vocoder.h"
 #include "vv_dsp/spectral/hpss.h"
+#include "vv_dsp/spectral/denoise.h"
 #endif

@@ -22,6 +22,7 @@
 #include "vv_dsp/spectral/czt.h"
 #include "vv_dsp/spectral/phase_vocoder.h"
 #include "vv_dsp/spectral/hpss.h"
+#include "vv_dsp/spectral/denoise.h"
 #include "vv_dsp/envelope/cepstrum.h"
 #include "vv_dsp/envelope/minphase.h"
 #include "vv_dsp/envelope/lpc.h"
@@ -565,6 +566,40 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_stft_hpss_device(vv_dsp_stft* h, const vv_
                                                        size_t ch_stride, vv_dsp_real* d_out_harm,
                                                        vv_dsp_real* d_out_perc, size_t out_ch_stride, void* stream,
                                                        size_t* out_len);
+/* Spectral noise suppression (vv_dsp/spectral/denoise.h, which states every
+ * value's definition and the argument checks, made in its order before any
+ * device work).
+ * _denoise_: `rows` rows of n_fft/2 + 1 powers, row_pitch floats apart, in groups
+ * of rows_per_group rows (0: one group; the last may be short) -> the planes of
+ * `out` that are not NULL, [rows][out_pitch], the pads past bin n_fft/2 neither
+ * read nor written.  One launch: a block walks a segment of a group's rows for 64
+ * consecutive bins with the smoothed halo of the segment in LDS; no scratch.
+ * Knobs DENOISE_SEGMENT = L (the segment length) and DENOISE_MIN = 1 / 2 (the
+ * direct / the blockwise minimum) change no value.
+ * _stft_denoise_: d_signal [nch][n] (ch_stride floats apart) -> d_out
+ * [nch][out_len] (out_ch_stride floats apart), out_len = (T - 1) hop + fft_size
+ * with T the handle's frame count of n samples (a signal shorter than one frame
+ * is one zero-padded frame, as everywhere in the STFT):
+ * vv_dsp_stft_power_device rows; vv_dsp_denoise_device gain, one group per
+ * channel; vv_dsp_stft_spectrum_device rows whose bin k has its real and its
+ * imaginary part each multiplied in float by gain[k] (bin n_fft - k by the same
+ * gain); vv_dsp_stft_reconstruct_device of each channel's rows into zeroed out and
+ * norm; y[i] = norm[i] > VV_DSP_PVOC_NORM_FLOOR ? out[i] / norm[i] : 0 -- the
+ * values of the public calls in sequence, bit for bit.  The rows live in
+ * stream-ordered scratch, a group of channels at a time (as many as fit 1 GiB, at
+ * least one; knob DENOISE_GROUP = k: k channels per group; the result does not
+ * depend on it).  Checks in this order, as vv_dsp_stft_hpss_device orders its
+ * own: NULL handle, params, signal or output; fft_size < 2, params->n_fft !=
+ * fft_size, ch_stride < n (for nch > 1 only) or out_ch_stride < out_len (for one
+ * channel too) -- INVALID_SIZE; then checks 3 and 4 of denoise.h.  *out_len (may
+ * be NULL) is set once every check has passed; nch == 0: OK. */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_denoise_device(const vv_dsp_real* d_power, size_t rows, size_t row_pitch,
+                                                     size_t rows_per_group, const vv_dsp_denoise_params* params,
+                                                     const vv_dsp_denoise_out* out, size_t out_pitch, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_stft_denoise_device(vv_dsp_stft* h, const vv_dsp_denoise_params* params,
+                                                          const vv_dsp_real* d_signal, size_t n, size_t nch,
+                                                          size_t ch_stride, vv_dsp_real* d_out, size_t out_ch_stride,
+                                                          void* stream, size_t* out_len);
 /* Biquad cascade on `batch` rows of n samples, x_stride / y_stride floats apart
  * (vv_dsp/filter/iir.h, iir.c:21-43).  d_coef [num_stages][5] = b0 b1 b2 a1 a2
  * per stage, one cascade for every row.  d_state [batch][num_stages][2] = z1 z2

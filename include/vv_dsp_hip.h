@@ -38,6 +38,8 @@
  *                  include/vv_dsp/spectral/phase_vocoder.h defines them
  *   vvhip_medfilt_* / _hpss_* / _stft_hpss_*: no reference source;
  *                  include/vv_dsp/filter/median.h and spectral/hpss.h define them
+ *   vvhip_denoise_* / _stft_denoise_*: no reference source;
+ *                  include/vv_dsp/spectral/denoise.h defines them
  */
 #ifndef VV_DSP_HIP_H
 #define VV_DSP_HIP_H
@@ -545,6 +547,34 @@ int vvhip_hpss_host(const float* power_rows, size_t rows, const vvhip_hpss_param
 int vvhip_stft_hpss_device(vvhip_stft* h, const vvhip_hpss_params* params, const float* d_signal, size_t n, size_t nch,
                            size_t ch_stride, float* d_out_harm, float* d_out_perc, size_t out_ch_stride,
                            void* stream, size_t* out_len);
+
+/* ---- Spectral noise suppression (include/vv_dsp/spectral/denoise.h: the
+ * definition and the checks, made in its order before any device work;
+ * denoise_kernels.hip) ----
+ * vvhip_denoise_params / vvhip_denoise_out: the layouts of vv_dsp_denoise_params
+ * and _out.  _denoise_: power rows -> the planes that are wanted, one launch;
+ * _denoise_host: one group of packed rows in host memory.  _stft_denoise_: signal
+ * [nch][n] -> the denoised signal [nch][out_len], in channel groups (knob
+ * DENOISE_GROUP = k: k channels per group).  Knobs DENOISE_SEGMENT = L (the
+ * segment length of the walk down the rows) and DENOISE_MIN = 1 / 2 (the direct /
+ * the blockwise minimum) change no value; STAT_DENOISE counts the launches. */
+typedef struct vvhip_denoise_params {
+    size_t n_fft;
+    int smooth_len, back, ahead;
+    float bias, floor;
+    int mode;
+} vvhip_denoise_params;
+typedef struct vvhip_denoise_out {
+    float *smooth, *noise, *gain;
+} vvhip_denoise_out;
+int vvhip_denoise_device(const float* d_power, size_t rows, size_t row_pitch, size_t rows_per_group,
+                         const vvhip_denoise_params* params, const vvhip_denoise_out* out, size_t out_pitch,
+                         void* stream);
+int vvhip_denoise_host(const float* power_rows, size_t rows, const vvhip_denoise_params* params,
+                       const vvhip_denoise_out* out);
+int vvhip_stft_denoise_device(vvhip_stft* h, const vvhip_denoise_params* params, const float* d_signal, size_t n,
+                              size_t nch, size_t ch_stride, float* d_out, size_t out_ch_stride, void* stream,
+                              size_t* out_len);
 
 /* ---- Spectral utilities (src/spectral/utils.c:5-73) ----
  * `batch` contiguous rows of n: fftshift (inverse 0) / ifftshift (inverse 1) of

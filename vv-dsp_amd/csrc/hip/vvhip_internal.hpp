@@ -18,11 +18,11 @@ enum Knob : int {
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
-    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_SHAPE_DWORD, KNOB_PVOC_GROUP, KNOB_PVOC_PLANE, KNOB_PTRACK_GROUP, KNOB_MEDIAN_SELECT, KNOB_HPSS_GROUP, KNOB_COUNT
+    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_SHAPE_DWORD, KNOB_PVOC_GROUP, KNOB_PVOC_PLANE, KNOB_PTRACK_GROUP, KNOB_MEDIAN_SELECT, KNOB_HPSS_GROUP, KNOB_DENOISE_SEGMENT, KNOB_DENOISE_MIN, KNOB_DENOISE_GROUP, KNOB_COUNT
 };
 long long knob(Knob k, long long dflt);
 // launches of the paths the tests must see taken (vvhip_debug_get("STAT_..."))
-enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_PITCH_WAVE, STAT_SHAPE_WAVE, STAT_SHAPE_VEC16, STAT_PVOC_ROWS, STAT_PITCH_TRACK, STAT_COUNT };
+enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_PITCH_WAVE, STAT_SHAPE_WAVE, STAT_SHAPE_VEC16, STAT_PVOC_ROWS, STAT_PITCH_TRACK, STAT_DENOISE, STAT_COUNT };
 void stat_inc(Stat s);
 
 // Device-resident W_N^k = exp(-2*pi*i*k/N) table, k < N, f32 rounded from double.
@@ -538,6 +538,25 @@ hipError_t launch_med_cols(const MedArgs& a, hipStream_t s);
 // spec rows [rows][n_fft] float pairs times mask [rows][K] (bin j >= K by mask[n_fft - j]) -> out
 hipError_t launch_hpss_apply(const float2* spec, const float* mask, float2* out, long long rows, long long n_fft,
                              hipStream_t s);
+
+// ---- spectral noise suppression (denoise_kernels.hip), include/vv_dsp/spectral/denoise.h ----
+constexpr int DN_MAX_SMOOTH = 64;                 // VV_DSP_DENOISE_MAX_SMOOTH
+constexpr int DN_MAX_REACH = 511;                 // VV_DSP_DENOISE_MAX_REACH
+constexpr int DN_THREADS = 512;                   // eight waves share one halo of smoothed rows
+constexpr int DN_DIRECT_BELOW = 64;               // windows below this: the direct minimum, else blockwise
+enum DenoiseMode : int { DN_GATE, DN_WIENER, DN_SUBTRACT };
+// One launch.  Powers p[row * p_pitch + k], k < K, rows in groups of rpg (> 0) consecutive rows.
+// seg (0: chosen by the launcher) is the segment length L; direct: 1 the direct minimum, 0 blockwise.
+struct DenoiseArgs {
+    const float* p = nullptr;
+    long long rows = 0, K = 0, p_pitch = 0, rpg = 0;
+    int W = 1, back = 0, ahead = 0, mode = DN_WIENER;
+    double bias = 1.0, floor = 0.0;               // (double) of the float parameters
+    float *smooth = nullptr, *noise = nullptr, *gain = nullptr;   // each null (not wanted) or [row * o_pitch + k]
+    long long o_pitch = 0;
+    int seg = 0, direct = 0;
+};
+hipError_t launch_denoise(const DenoiseArgs& a, hipStream_t s);
 
 // ---- biquad cascade (iir_kernels.hip), src/filter/iir.c:21-43 -----------------
 constexpr int IIR_MAX_STAGES = 8;        // stages one walk holds in registers; longer cascades run in groups

@@ -100,6 +100,22 @@ class HpssOut(C.Structure):
 
 HPSS_NAMES = tuple(name for name, _ in HpssOut._fields_)
 
+DENOISE_GATE, DENOISE_WIENER, DENOISE_SUBTRACT = 0, 1, 2
+
+
+class DenoiseParams(C.Structure):
+    """vv_dsp_denoise_params (vv_dsp/spectral/denoise.h)"""
+    _fields_ = [("n_fft", C.c_size_t), ("smooth_len", C.c_int), ("back", C.c_int), ("ahead", C.c_int),
+                ("bias", C.c_float), ("floor", C.c_float), ("mode", C.c_int)]
+
+
+class DenoiseOut(C.Structure):
+    """vv_dsp_denoise_out: one device pointer per plane, NULL = not wanted"""
+    _fields_ = [(name, C.c_void_p) for name in ("smooth", "noise", "gain")]
+
+
+DENOISE_NAMES = tuple(name for name, _ in DenoiseOut._fields_)
+
 
 class VvError(RuntimeError):
     pass
@@ -226,6 +242,11 @@ def lib():
     L.vv_dsp_hpss_device.argtypes = [_vp, _sz, _sz, _sz, C.POINTER(HpssParams), C.POINTER(HpssOut), _sz, _vp]
     L.vv_dsp_stft_hpss_device.argtypes = [_vp, C.POINTER(HpssParams), _vp, _sz, _sz, _sz, _vp, _vp, _sz, _vp,
                                           C.POINTER(_sz)]
+    L.vv_dsp_denoise_params_default.argtypes = [_sz, C.POINTER(DenoiseParams)]
+    L.vv_dsp_denoise.argtypes = [_vp, _sz, C.POINTER(DenoiseParams), C.POINTER(DenoiseOut)]
+    L.vv_dsp_denoise_device.argtypes = [_vp, _sz, _sz, _sz, C.POINTER(DenoiseParams), C.POINTER(DenoiseOut), _sz, _vp]
+    L.vv_dsp_stft_denoise_device.argtypes = [_vp, C.POINTER(DenoiseParams), _vp, _sz, _sz, _sz, _vp, _sz, _vp,
+                                             C.POINTER(_sz)]
     L.vv_dsp_iir_apply_device.argtypes =[_vp, _sz, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]
     L.vv_dsp_savgol_coeffs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, _vp]
     L.vv_dsp_savgol_device.argtypes = [_vp, _sz, _sz, _sz, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp, _sz,
@@ -468,6 +489,25 @@ class Stft:
                                                  _stream(stream), C.byref(got)), "stft_hpss_device")
             assert got.value == ln
         return tuple(o if o is None or sig.dim() == 2 else o[0] for o in outs)
+
+    def denoise(self, sig, params, stream=None):
+        """sig: (nch, n) or (n,) float32 -> the signal with its stationary noise floor
+        suppressed, (nch, out_len) or (out_len,), out_len = (frames - 1) * hop + nfft:
+        power() -> denoise() gain -> spectrogram(complex_out=True) times the gain ->
+        reconstruct() into zeros -> out / norm, in one call with the rows in stream-ordered
+        scratch (vv_dsp_stft_denoise_device), bit-identical to those steps."""
+        if not isinstance(params, DenoiseParams):
+            raise VvError("stft denoise: params must be a DenoiseParams")
+        sig2, nch, n = _signal(sig, "stft denoise")
+        ln = (self.frames(n) - 1) * self.hop + self.nfft
+        out = torch.empty((nch, ln), dtype=torch.float32, device=sig.device)
+        got = _sz(0)
+        if nch:
+            _check(lib().vv_dsp_stft_denoise_device(self.h, C.byref(params), _vp(sig2.data_ptr()), n, nch,
+                                                    sig2.stride(0), _vp(out.data_ptr()), ln, _stream(stream),
+                                                    C.byref(got)), "stft_denoise_device")
+            assert got.value == ln
+        return out if sig.dim() == 2 else out[0]
 
     def frames_range(self, sig, frame0, nframes, kind=0, out=None, stream=None):
         """Rows of frames [frame0, frame0 + nframes) of sig's spectrogram (one shard
@@ -1367,6 +1407,57 @@ def hpss(power, params, what, rows_per_group=0, stream=None):
     if planes and rows:
         _check(lib().vv_dsp_hpss_device(_vp(power.data_ptr()), rows, pitch, rows_per_group, C.byref(params),
                                         C.byref(out), nb, _stream(stream)), "hpss_device")
+    return planes
+
+
+def denoise_params(n_fft, **fields):
+    """the default parameters for rows of n_fft//2 + 1 bins (vv_dsp_denoise_params_default:
+    smooth_len 8, back 48, ahead 48, bias 4, floor 0.1, WIENER; host arithmetic, needs no
+    device), with the fields given by name replaced"""
+    prm = DenoiseParams()
+    _check(lib().vv_dsp_denoise_params_default(n_fft, C.byref(prm)), "denoise_params_default")
+    for name, value in fields.items():
+        if name not in dict(DenoiseParams._fields_):
+            raise VvError(f"denoise_params: unknown field {name!r}")
+        setattr(prm, name, value)
+    return prm
+
+
+def denoise(power, params, what="gain", rows_per_group=0, stream=None):
+    """Minimum-statistics noise floor and gain of float32 device power rows
+    (vv_dsp/spectral/denoise.h): power (rows, pitch) or (ch, frames, pitch), the rows
+    power.stride(-2) >= n_fft//2 + 1 floats apart (bins 0..n_fft//2 of each are read) ->
+    {name: tensor (rows, n_fft//2 + 1) or (ch, frames, n_fft//2 + 1)} for the names in
+    `what` (DENOISE_NAMES: smooth, noise, gain), one launch.  A (ch, frames, pitch) tensor
+    is ch groups of `frames` rows; for (rows, pitch), rows_per_group rows form a group (0: one)."""
+    if not isinstance(params, DenoiseParams):
+        raise VvError("denoise: params must be a DenoiseParams")
+    if power.dim() not in (2, 3) or power.dtype != torch.float32 or not power.is_cuda:
+        raise VvError("denoise: float32 device rows (rows, pitch) or (ch, frames, pitch)")
+    nb = params.n_fft // 2 + 1
+    lead = tuple(power.shape[:-1])
+    rows = 1
+    for d in lead:
+        rows *= d
+    pitch = power.stride(-2) if power.shape[-2] > 1 else power.shape[-1]
+    if power.shape[-1] < nb or (power.shape[-1] > 1 and power.stride(-1) != 1) or pitch < nb:
+        raise VvError(f"denoise: rows of {power.shape[-1]} floats, pitch {pitch}, for {nb} bins")
+    if power.dim() == 3:
+        if power.shape[0] > 1 and power.stride(0) != power.shape[1] * pitch:
+            raise VvError("denoise: channels must follow each other, frames x pitch floats apart")
+        rows_per_group = power.shape[1]
+    if isinstance(what, str):
+        what = (what,)
+    planes, out = {}, DenoiseOut()
+    for name in what:
+        if name not in DENOISE_NAMES:
+            raise VvError(f"denoise: unknown output {name!r} (one of {', '.join(DENOISE_NAMES)})")
+        if name not in planes:
+            planes[name] = torch.empty(lead + (nb,), dtype=torch.float32, device=power.device)
+            setattr(out, name, planes[name].data_ptr())
+    if planes and rows:
+        _check(lib().vv_dsp_denoise_device(_vp(power.data_ptr()), rows, pitch, rows_per_group, C.byref(params),
+                                           C.byref(out), nb, _stream(stream)), "denoise_device")
     return planes
 
 
