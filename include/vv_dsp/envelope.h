@@ -1,10 +1,11 @@
-/* envelope.h -- the envelope module: real cepstrum, minimum phase, LPC
+/* envelope.h -- the envelope module: real cepstrum, minimum phase, LPC, LSF
  * (reference include/vv_dsp/envelope.h). */
 #ifndef VV_DSP_ENVELOPE_H
 #define VV_DSP_ENVELOPE_H
 #include "vv_dsp/envelope/cepstrum.h"
 #include "vv_dsp/envelope/minphase.h"
 #include "vv_dsp/envelope/lpc.h"
+#include "vv_dsp/envelope/lsf.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -18,6 +18,7 @@
 #include "vv_dsp/features/mel.h"
 #include "vv_dsp/features/pitch.h"
 #include "vv_dsp/features/pitch_track.h"
+#include "vv_dsp/features/formant.h"
 #include "vv_dsp/features/spectral_shape.h"
 #include "vv_dsp/spectral/czt.h"
 #include "vv_dsp/spectral/phase_vocoder.h"
@@ -26,6 +27,7 @@
 #include "vv_dsp/envelope/cepstrum.h"
 #include "vv_dsp/envelope/minphase.h"
 #include "vv_dsp/envelope/lpc.h"
+#include "vv_dsp/envelope/lsf.h"
 #include "vv_dsp/resample/resampler.h"
 #include "vv_dsp/resample/interpolate.h"
 #include "vv_dsp/core/stats.h"
@@ -325,6 +327,41 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpc_frames_device(const vv_dsp_real* d_sig
 VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpspec_device(const vv_dsp_real* d_a, size_t order, const vv_dsp_real* d_gain,
                                                     size_t nfft, size_t batch, int levinson_sign, vv_dsp_real* d_mag,
                                                     void* stream);
+/* Line spectral frequencies, reflection coefficients and formants of LPC rows
+ * (vv_dsp/envelope/lsf.h and vv_dsp/features/formant.h, which state the
+ * definitions and the order of the checks).
+ * _lpc_to_lsf_: d_a [batch] rows a_pitch floats apart (a_pitch >= order + 1, so
+ * rows of vv_dsp_lpc_frames_device feed it directly) -> d_lsf and d_rc packed
+ * [batch][order], d_flags [batch] int32 (VV_DSP_LSF_STABLE | _COMPLETE); any
+ * output may be NULL, not all.  _lsf_to_lpc_: d_lsf packed [batch][order] -> d_a
+ * rows a_pitch floats apart.
+ * _lpc_formants_: d_a as above -> the planes of vv_dsp_formant_out, packed by row.
+ * _lsf_frames_ / _formants_frames_: the signal arguments of
+ * vv_dsp_lpc_frames_device; the LPC rows go to stream-ordered scratch in groups
+ * of channels and are converted from there, bit-identical to
+ * vv_dsp_lpc_frames_device followed by the row call.  lsf and rc are
+ * [nch][frames][order], flags and err [nch][frames]; the formant planes are
+ * [nch * frames] rows, channel-major; each may be NULL, not all.  Zero frames: OK,
+ * nothing written.  Zero rows: OK, nothing launched.
+ * vvhip_debug_get("STAT_LSF") / ("STAT_FORMANT") count the launches. */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpc_to_lsf_device(const vv_dsp_real* d_a, size_t order, size_t batch,
+                                                        size_t a_pitch, vv_dsp_real* d_lsf, vv_dsp_real* d_rc,
+                                                        int32_t* d_flags, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_lsf_to_lpc_device(const vv_dsp_real* d_lsf, size_t order, size_t batch,
+                                                        vv_dsp_real* d_a, size_t a_pitch, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_lsf_frames_device(const vv_dsp_real* d_signal, size_t n, size_t nch,
+                                                        size_t ch_stride, size_t frame_len, size_t hop_len, int center,
+                                                        const vv_dsp_real* d_window, size_t order, vv_dsp_real* d_lsf,
+                                                        vv_dsp_real* d_rc, int32_t* d_flags, vv_dsp_real* d_err,
+                                                        void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpc_formants_device(const vv_dsp_real* d_a, size_t order, size_t batch,
+                                                          size_t a_pitch, const vv_dsp_formant_params* params,
+                                                          const vv_dsp_formant_out* out, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_formants_frames_device(const vv_dsp_real* d_signal, size_t n, size_t nch,
+                                                             size_t ch_stride, size_t frame_len, size_t hop_len,
+                                                             int center, const vv_dsp_real* d_window, size_t order,
+                                                             const vv_dsp_formant_params* params,
+                                                             const vv_dsp_formant_out* out, void* stream);
 /* Array statistics (vv_dsp/core/stats.h, which states the numerics: the exact
  * class bit-identical to the reference, the f64 class within 1 ulp of it, one
  * summation order whatever the batch, stride, outputs or entry point).

@@ -576,6 +576,42 @@ int vvhip_stft_denoise_device(vvhip_stft* h, const vvhip_denoise_params* params,
                               size_t nch, size_t ch_stride, float* d_out, size_t out_ch_stride, void* stream,
                               size_t* out_len);
 
+/* ---- LSF, reflection coefficients and formants of LPC rows
+ * (include/vv_dsp/envelope/lsf.h, include/vv_dsp/features/formant.h; entry
+ * points as vv_dsp_amd.h's, `frames` per channel given by the caller) ----
+ * vvhip_formant_params / vvhip_formant_out: the layouts of vv_dsp_formant_params
+ * and vv_dsp_formant_out.  "STAT_LSF" / "STAT_FORMANT" count the launches of
+ * lsf_kernels.hip / formant_kernels.hip; knob LSF_GROUP = g > 0 forces channel
+ * groups of g in the two _frames_ calls. */
+typedef struct vvhip_formant_params {
+    float sample_rate, f_min, f_max, bw_max;
+    uint32_t n_formants;
+} vvhip_formant_params;
+typedef struct vvhip_formant_out {
+    float* freq;
+    float* bw;
+    int32_t* count;
+    int32_t* flags;
+    double* roots;
+} vvhip_formant_out;
+int vvhip_lpc_to_lsf_device(const float* d_a, size_t order, size_t batch, size_t a_pitch, float* d_lsf, float* d_rc,
+                            int32_t* d_flags, void* stream);
+int vvhip_lsf_to_lpc_device(const float* d_lsf, size_t order, size_t batch, float* d_a, size_t a_pitch, void* stream);
+int vvhip_lsf_frames_device(const float* d_signal, size_t n, size_t nch, size_t ch_stride, size_t frame_len,
+                            size_t hop, size_t frames, int center, const float* d_window, size_t order, float* d_lsf,
+                            float* d_rc, int32_t* d_flags, float* d_err, void* stream);
+int vvhip_lpc_to_lsf_host(const float* a, size_t order, float* lsf, float* rc, int32_t* flags);
+int vvhip_lsf_to_lpc_host(const float* lsf, size_t order, float* a);
+int vvhip_formant_params_default(float sample_rate, vvhip_formant_params* params);
+int vvhip_formant_start_points(size_t order, double* out);
+int vvhip_lpc_formants_device(const float* d_a, size_t order, size_t batch, size_t a_pitch,
+                              const vvhip_formant_params* params, const vvhip_formant_out* out, void* stream);
+int vvhip_formants_frames_device(const float* d_signal, size_t n, size_t nch, size_t ch_stride, size_t frame_len,
+                                 size_t hop, size_t frames, int center, const float* d_window, size_t order,
+                                 const vvhip_formant_params* params, const vvhip_formant_out* out, void* stream);
+int vvhip_lpc_formants_host(const float* a, size_t order, const vvhip_formant_params* params,
+                            const vvhip_formant_out* out);
+
 /* ---- Spectral utilities (src/spectral/utils.c:5-73) ----
  * `batch` contiguous rows of n: fftshift (inverse 0) / ifftshift (inverse 1) of
  * float (cpx 0) or complex (cpx 1) rows, a permutation (in place allowed);

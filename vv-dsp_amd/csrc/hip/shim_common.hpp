@@ -313,6 +313,10 @@ struct FramesCall {
     }
 };
 
+// ---- shim_lsf.hip: channels per group of the signal -> LSF / formant calls,
+// whose LPC rows take per_ch bytes of scratch a channel (knob LSF_GROUP) ----
+size_t lsf_group(size_t per_ch, size_t nch);
+
 // ---- shim_fft.hip: the FFT dispatch every other module transforms through ----
 // Non-power-of-two DFT: the mixed-radix kernel for 7-smooth n <= 4096, else the
 // exact-angle f64 O(n^2) kernel for short lengths and Bluestein over the

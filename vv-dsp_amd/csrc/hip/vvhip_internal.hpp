@@ -18,11 +18,11 @@ enum Knob : int {
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
-    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_SHAPE_DWORD, KNOB_PVOC_GROUP, KNOB_PVOC_PLANE, KNOB_PTRACK_GROUP, KNOB_MEDIAN_SELECT, KNOB_HPSS_GROUP, KNOB_DENOISE_SEGMENT, KNOB_DENOISE_MIN, KNOB_DENOISE_GROUP, KNOB_COUNT
+    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_SHAPE_DWORD, KNOB_PVOC_GROUP, KNOB_PVOC_PLANE, KNOB_PTRACK_GROUP, KNOB_MEDIAN_SELECT, KNOB_HPSS_GROUP, KNOB_DENOISE_SEGMENT, KNOB_DENOISE_MIN, KNOB_DENOISE_GROUP, KNOB_LSF_GROUP, KNOB_COUNT
 };
 long long knob(Knob k, long long dflt);
 // launches of the paths the tests must see taken (vvhip_debug_get("STAT_..."))
-enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_PITCH_WAVE, STAT_SHAPE_WAVE, STAT_SHAPE_VEC16, STAT_PVOC_ROWS, STAT_PITCH_TRACK, STAT_DENOISE, STAT_COUNT };
+enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_PITCH_WAVE, STAT_SHAPE_WAVE, STAT_SHAPE_VEC16, STAT_PVOC_ROWS, STAT_PITCH_TRACK, STAT_DENOISE, STAT_LSF, STAT_FORMANT, STAT_COUNT };
 void stat_inc(Stat s);
 
 // Device-resident W_N^k = exp(-2*pi*i*k/N) table, k < N, f32 rounded from double.
@@ -440,6 +440,32 @@ constexpr int ptrack_block(int S) {
 // forward pass (one wave per channel up to 64 states, one workgroup beyond) and
 // backtrace on stream s; nch > 0, F > 0, checked sizes
 hipError_t launch_pitch_track(const PtrackCfg& cfg, const PtrackArgs& a, hipStream_t s);
+
+// ---- LSF and formants of LPC rows (lsf_kernels.hip, formant_kernels.hip),
+// include/vv_dsp/envelope/lsf.h and include/vv_dsp/features/formant.h ----
+constexpr int LSF_MAX_ORDER = 32;   // VV_DSP_LSF_MAX_ORDER = VV_DSP_FORMANT_MAX_ORDER
+// a [rows] a_pitch floats apart -> lsf, rc [rows][order], flags [rows]; null: not wanted.
+// One wave per row; 1 <= order <= LSF_MAX_ORDER, rows > 0.
+hipError_t launch_lpc_to_lsf(const float* a, int order, long long rows, long long a_pitch, float* lsf, float* rc,
+                             int* flags, hipStream_t s);
+// lsf [rows][order] -> a [rows] a_pitch floats apart; one wave per row
+hipError_t launch_lsf_to_lpc(const float* lsf, int order, long long rows, float* a, long long a_pitch, hipStream_t s);
+struct FormantCfg {
+    double sample_rate = 0.0, f_min = 0.0, f_max = 0.0, bw_max = 0.0;
+    int n_formants = 0;
+    double start[2 * LSF_MAX_ORDER];   // vvhip_formant_start_points(order)
+};
+struct FormantOut {
+    float* freq = nullptr;
+    float* bw = nullptr;
+    int* count = nullptr;
+    int* flags = nullptr;
+    double* roots = nullptr;
+};
+// a [rows] a_pitch floats apart -> the planes of out, packed by row.  One lane
+// per root, 8 / 4 / 2 rows per wave for orders up to 8 / 16 / 32.
+hipError_t launch_formants(const float* a, int order, long long rows, long long a_pitch, const FormantCfg& cfg,
+                           const FormantOut& out, hipStream_t s);
 
 // ---- per-frame spectral shape (shape_kernels.hip), include/vv_dsp/features/spectral_shape.h ----
 constexpr int SHAPE_MAX_BINS = 8193;             // K = n_fft / 2 + 1 of a row

@@ -69,6 +69,24 @@ class PitchTrackOut(C.Structure):
 TRACK_NAMES = tuple(name for name, _ in PitchTrackOut._fields_)
 
 
+class FormantParams(C.Structure):
+    """vv_dsp_formant_params (vv_dsp/features/formant.h)"""
+    _fields_ = [("sample_rate", C.c_float), ("f_min", C.c_float), ("f_max", C.c_float), ("bw_max", C.c_float),
+                ("n_formants", C.c_uint32)]
+
+
+class FormantOut(C.Structure):
+    """vv_dsp_formant_out: one device pointer per output, NULL = not wanted"""
+    _fields_ = [(name, C.c_void_p) for name in ("freq", "bw", "count", "flags", "roots")]
+
+
+FORMANT_NAMES = tuple(name for name, _ in FormantOut._fields_)
+LSF_NAMES = ("lsf", "rc", "flags")
+LSF_STABLE, LSF_COMPLETE = 1, 2          # bits of the lsf flags word
+FORMANT_CONVERGED = 1                    # bit of the formant flags word
+LSF_MAX_ORDER = 32
+
+
 class SpectralShapeParams(C.Structure):
     """vv_dsp_spectral_shape_params (vv_dsp/features/spectral_shape.h)"""
     _fields_ = [("n_fft", C.c_size_t), ("sample_rate", C.c_float), ("magnitude", C.c_int), ("k_min", C.c_size_t),
@@ -209,6 +227,17 @@ def lib():
     L.vv_dsp_lpc_device.argtypes = [_vp, _sz, _sz, _sz, _vp, _vp, _vp]
     L.vv_dsp_lpc_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, _sz, _vp, _sz, _vp, _sz, _vp]
     L.vv_dsp_lpspec_device.argtypes = [_vp, _sz, _vp, _sz, _sz, C.c_int, _vp, _vp]
+    L.vv_dsp_lpc_to_lsf_device.argtypes = [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp]
+    L.vv_dsp_lsf_to_lpc_device.argtypes = [_vp, _sz, _sz, _vp, _sz, _vp]
+    L.vv_dsp_lsf_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
+    L.vv_dsp_lpc_to_lsf.argtypes = [_vp, _sz, _vp, _vp, _vp]
+    L.vv_dsp_lsf_to_lpc.argtypes = [_vp, _sz, _vp]
+    L.vv_dsp_formant_params_default.argtypes = [C.c_float, C.POINTER(FormantParams)]
+    L.vv_dsp_formant_start_points.argtypes = [_sz, _vp]
+    L.vv_dsp_lpc_formants.argtypes = [_vp, _sz, C.POINTER(FormantParams), C.POINTER(FormantOut)]
+    L.vv_dsp_lpc_formants_device.argtypes = [_vp, _sz, _sz, _sz, C.POINTER(FormantParams), C.POINTER(FormantOut), _vp]
+    L.vv_dsp_formants_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, _sz,
+                                                C.POINTER(FormantParams), C.POINTER(FormantOut), _vp]
     L.vv_dsp_stats_device.argtypes = [_vp, _sz, _sz, _sz, C.POINTER(StatsOut), _vp]
     L.vv_dsp_stats_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, C.POINTER(StatsOut), _sz, _vp]
     L.vv_dsp_autocorrelation_device.argtypes = [_vp, _sz, _sz, _sz, C.c_int, _vp, _vp]
@@ -948,6 +977,168 @@ def lpc_frames(sig, frame_len, hop, order, window=None, center=False, out=None, 
                                           _ptr(a), fr * (order + 1), _ptr(err), fr, _stream(stream)),
            "lpc_frames_device")
     return (a, err) if sig.dim() == 2 or out is not None else (a[0], err[0])
+
+
+def _lpc_rows(a, order, who):
+    """(a2, batch, order, pitch) of LPC rows (batch, w) or (w,), w >= order + 1 (order None: w - 1),
+    rows a.stride(0) floats apart"""
+    a2 = a if a.dim() == 2 else a.unsqueeze(0)
+    if a.dim() not in (1, 2) or a2.dtype != torch.float32 or not a2.is_cuda or \
+            (a2.numel() and a2.stride(1) != 1):   # an empty batch has no strides to speak of
+        raise VvError(f"{who}: float32 device rows (batch, order + 1) or (order + 1,) with unit stride")
+    batch, w = a2.shape
+    order = w - 1 if order is None else int(order)
+    if order < 1 or order > LSF_MAX_ORDER or order + 1 > w:
+        raise VvError(f"{who}: order {order} for rows of {w} coefficients (1..{LSF_MAX_ORDER})")
+    pitch = a2.stride(0) if batch > 1 else max(w, a2.stride(0))
+    if batch and pitch < order + 1:
+        raise VvError(f"{who}: overlapping rows")
+    return a2, batch, order, pitch
+
+
+def _named(what, names, who):
+    what = (what,) if isinstance(what, str) else tuple(what)
+    for name in what:
+        if name not in names:
+            raise VvError(f"{who}: unknown output {name!r} (one of {', '.join(names)})")
+    if not what:
+        raise VvError(f"{who}: no output wanted")
+    return what
+
+
+def _lsf_planes(what, rows_shape, order, device, who, names=LSF_NAMES):
+    planes = {}
+    for name in _named(what, names, who):
+        if name in ("lsf", "rc"):
+            planes[name] = torch.empty(rows_shape + (order,), dtype=torch.float32, device=device)
+        else:
+            planes[name] = torch.empty(rows_shape, dtype=torch.int32 if name == "flags" else torch.float32,
+                                       device=device)
+    return planes
+
+
+def _opt(planes, name):
+    return _vp(planes[name].data_ptr()) if name in planes else None
+
+
+def lpc_to_lsf(a, what=LSF_NAMES, order=None, stream=None):
+    """LPC rows (batch, w) or (w,) float32, A(z) = 1 + sum a[m] z^-m (levinson's / lpc_frames'
+    rows; rows a.stride(0) floats apart, order = w - 1 unless given) -> {name: tensor} for the
+    names in `what` (LSF_NAMES): lsf (batch, order) radians ascending, NaN rows where the scan is
+    not complete; rc (batch, order) reflection coefficients; flags (batch,) int32, LSF_STABLE |
+    LSF_COMPLETE (vv_dsp/envelope/lsf.h)."""
+    a2, batch, order, pitch = _lpc_rows(a, order, "lpc_to_lsf")
+    planes = _lsf_planes(what, (batch,), order, a.device, "lpc_to_lsf")
+    if batch:
+        _check(lib().vv_dsp_lpc_to_lsf_device(_vp(a2.data_ptr()), order, batch, pitch, _opt(planes, "lsf"),
+                                              _opt(planes, "rc"), _opt(planes, "flags"), _stream(stream)),
+               "lpc_to_lsf_device")
+    return _planes_of(planes, a)
+
+
+def lsf_to_lpc(lsf, out=None, stream=None):
+    """LSF rows (batch, order) or (order,) float32 radians -> {"a": (batch, order + 1)}, a[0] = 1.
+    out: a (batch, w >= order + 1) tensor whose rows (out.stride(0) apart) take the coefficients."""
+    l2 = lsf if lsf.dim() == 2 else lsf.unsqueeze(0)
+    if lsf.dim() not in (1, 2) or l2.dtype != torch.float32 or not l2.is_cuda or not l2.is_contiguous():
+        raise VvError("lsf_to_lpc: contiguous float32 device rows (batch, order) or (order,)")
+    batch, order = l2.shape
+    if order < 1 or order > LSF_MAX_ORDER:
+        raise VvError(f"lsf_to_lpc: order {order} (1..{LSF_MAX_ORDER})")
+    a = torch.empty((batch, order + 1), dtype=torch.float32, device=lsf.device) if out is None else out
+    a2, ob, _, pitch = _lpc_rows(a if a.dim() == 2 else a.unsqueeze(0), order, "lsf_to_lpc out")
+    if ob < batch:
+        raise VvError(f"lsf_to_lpc out: {ob} rows, {batch} needed")
+    if batch:
+        _check(lib().vv_dsp_lsf_to_lpc_device(_vp(l2.data_ptr()), order, batch, _vp(a2.data_ptr()), pitch,
+                                              _stream(stream)), "lsf_to_lpc_device")
+    return {"a": a2[:, :order + 1] if lsf.dim() == 2 else a2[0, :order + 1]}
+
+
+def lsf_frames(sig, frame_len, hop, order, what=LSF_NAMES + ("err",), window=None, center=False, stream=None):
+    """Signal (nch, n) or (n,) float32 -> {name: tensor}: lsf, rc (nch, frames, order), flags, err
+    (nch, frames).  lpc_frames into scratch rows and lpc_to_lsf, in channel groups, bit-identical to
+    the two calls (vv_dsp_lsf_frames_device)."""
+    sig2, nch, n = _signal(sig, "lsf_frames")
+    if frame_len <= 0 or hop <= 0 or order < 1 or order > LSF_MAX_ORDER or order + 1 > frame_len:
+        raise VvError(f"lsf_frames: frame_len {frame_len}, hop {hop}, order {order}")
+    win = _window(window, frame_len, "lsf_frames")
+    fr = num_frames(n, frame_len, hop, center)
+    planes = _lsf_planes(what, (nch, fr), order, sig.device, "lsf_frames", LSF_NAMES + ("err",))
+    if fr and nch:
+        _check(lib().vv_dsp_lsf_frames_device(_vp(sig2.data_ptr()), n, nch, sig2.stride(0), frame_len, hop,
+                                              int(bool(center)), win, order, _opt(planes, "lsf"), _opt(planes, "rc"),
+                                              _opt(planes, "flags"), _opt(planes, "err"), _stream(stream)),
+               "lsf_frames_device")
+    return _planes_of(planes, sig)
+
+
+def formant_params(sample_rate, **fields):
+    """vv_dsp_formant_params_default (f_min 50 Hz, f_max sample_rate / 2 - 50, bw_max 600 Hz, 5
+    formants) with `fields` overridden; host arithmetic, needs no device"""
+    p = FormantParams()
+    _check(lib().vv_dsp_formant_params_default(float(sample_rate), C.byref(p)), "formant_params_default")
+    for k, v in fields.items():
+        if k not in dict(FormantParams._fields_):
+            raise VvError(f"formant_params: unknown field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def formant_start_points(order):
+    """the Aberth start points of `order` roots as a (order, 2) float64 host tensor
+    (vv_dsp_formant_start_points; host arithmetic, needs no device)"""
+    out = torch.empty((max(int(order), 0), 2), dtype=torch.float64)
+    _check(lib().vv_dsp_formant_start_points(int(order), _vp(out.data_ptr())), "formant_start_points")
+    return out
+
+
+def _formant_planes(params, what, rows_shape, order, device, who):
+    if not isinstance(params, FormantParams):
+        raise VvError(f"{who}: params must be a FormantParams")
+    if not 1 <= params.n_formants <= 16:
+        raise VvError(f"{who}: n_formants {params.n_formants} outside 1..16")
+    planes, out = {}, FormantOut()
+    for name in _named(what, FORMANT_NAMES, who):
+        if name in ("freq", "bw"):
+            planes[name] = torch.empty(rows_shape + (params.n_formants,), dtype=torch.float32, device=device)
+        elif name == "roots":
+            planes[name] = torch.empty(rows_shape + (order, 2), dtype=torch.float64, device=device)
+        else:
+            planes[name] = torch.empty(rows_shape, dtype=torch.int32, device=device)
+        setattr(out, name, planes[name].data_ptr())
+    return planes, out
+
+
+def formants(a, params, what=("freq", "bw", "count", "flags"), order=None, stream=None):
+    """LPC rows (batch, w) or (w,) float32 (as lpc_to_lsf takes them) -> {name: tensor} for the names
+    in `what` (FORMANT_NAMES): freq, bw (batch, n_formants) Hz, NaN past the count; count, flags
+    (batch,) int32 (FORMANT_CONVERGED); roots (batch, order, 2) float64, the poles of 1/A(z) by
+    Aberth-Ehrlich (vv_dsp/features/formant.h)."""
+    a2, batch, order, pitch = _lpc_rows(a, order, "formants")
+    planes, out = _formant_planes(params, what, (batch,), order, a.device, "formants")
+    if batch:
+        _check(lib().vv_dsp_lpc_formants_device(_vp(a2.data_ptr()), order, batch, pitch, C.byref(params),
+                                                C.byref(out), _stream(stream)), "lpc_formants_device")
+    return _planes_of(planes, a)
+
+
+def formant_frames(sig, frame_len, hop, order, params, what=("freq", "bw", "count", "flags"), window=None,
+                   center=False, stream=None):
+    """Signal (nch, n) or (n,) float32 -> the planes of formants() per frame, (nch, frames, ...):
+    lpc_frames into scratch rows and formants, in channel groups, bit-identical to the two calls
+    (vv_dsp_formants_frames_device).  Pre-emphasise the signal first where that is wanted."""
+    sig2, nch, n = _signal(sig, "formant_frames")
+    if frame_len <= 0 or hop <= 0 or order < 1 or order > LSF_MAX_ORDER or order + 1 > frame_len:
+        raise VvError(f"formant_frames: frame_len {frame_len}, hop {hop}, order {order}")
+    win = _window(window, frame_len, "formant_frames")
+    fr = num_frames(n, frame_len, hop, center)
+    planes, out = _formant_planes(params, what, (nch, fr), order, sig.device, "formant_frames")
+    if fr and nch:
+        _check(lib().vv_dsp_formants_frames_device(_vp(sig2.data_ptr()), n, nch, sig2.stride(0), frame_len, hop,
+                                                   int(bool(center)), win, order, C.byref(params), C.byref(out),
+                                                   _stream(stream)), "formants_frames_device")
+    return _planes_of(planes, sig)
 
 
 def lpspec(a, nfft, gain=None, levinson_sign=False, stream=None):
