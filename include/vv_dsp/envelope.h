@@ -1,4 +1,5 @@
-/* envelope.h -- the envelope module: real cepstrum, minimum phase, LPC, LSF
+/* envelope.h -- the envelope module: real cepstrum, minimum phase, LPC, LSF,
+ * the LPC residual and synthesis filters
  * (reference include/vv_dsp/envelope.h). */
 #ifndef VV_DSP_ENVELOPE_H
 #define VV_DSP_ENVELOPE_H
@@ -6,6 +7,7 @@
 #include "vv_dsp/envelope/minphase.h"
 #include "vv_dsp/envelope/lpc.h"
 #include "vv_dsp/envelope/lsf.h"
+#include "vv_dsp/envelope/lpc_filter.h"
 #ifdef __cplusplus
 extern "C" {
 #endif

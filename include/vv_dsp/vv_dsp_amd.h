@@ -28,6 +28,7 @@
 #include "vv_dsp/envelope/minphase.h"
 #include "vv_dsp/envelope/lpc.h"
 #include "vv_dsp/envelope/lsf.h"
+#include "vv_dsp/envelope/lpc_filter.h"
 #include "vv_dsp/resample/resampler.h"
 #include "vv_dsp/resample/interpolate.h"
 #include "vv_dsp/core/stats.h"
@@ -362,6 +363,45 @@ VV_DSP_NODISCARD vv_dsp_status vv_dsp_formants_frames_device(const vv_dsp_real* 
                                                              int center, const vv_dsp_real* d_window, size_t order,
                                                              const vv_dsp_formant_params* params,
                                                              const vv_dsp_formant_out* out, void* stream);
+/* LPC rows applied to a signal (vv_dsp/envelope/lpc_filter.h, which states the
+ * arithmetic, the row that governs a sample and the order of the checks).
+ * _lpc_residual_ / _lpc_synth_: signal [nch][n], channels x_stride floats apart,
+ * -> [nch][n], channels y_stride apart.  d_a: `frames` rows per channel, a_pitch
+ * >= order + 1 floats apart (rows of vv_dsp_lpc_frames_device and
+ * vv_dsp_lsf_to_lpc_device feed it directly), channels a_ch_stride apart;
+ * a_ch_stride == 0: one envelope for every channel.  d_gain: NULL (1), or
+ * [frames] floats per channel, channels g_ch_stride apart, 0 likewise.  d_state:
+ * NULL (zeros in, nothing out) or doubles [nch][order], read and overwritten.
+ * Synthesis may run in place (d_y == d_e); the residual may not.  Rows of n <=
+ * VV_DSP_LPC_SYNTH_EXACT_MAX are synthesised as one recursion, longer ones in
+ * chunks (knob LPC_SYNTH_CHUNK: 0 never chunks, k > 0 forces chunks of k).
+ * vvhip_debug_get("STAT_LPC_RESIDUAL") / ("STAT_LPC_SYNTH_EXACT") /
+ * ("STAT_LPC_SYNTH_CHUNKED") count the calls of each route.
+ * _lpc_residual_frames_: the signal arguments of vv_dsp_lpc_frames_device; the
+ * LPC rows go to d_a / d_err as that call lays them out, or, where one is NULL,
+ * to stream-ordered scratch in groups of channels; the residual of the signal
+ * through its own rows goes to d_e, with seg_len = hop_len and offset =
+ * hop_len / 2 when center, else hop_len / 2 - frame_len / 2 (the frame whose
+ * centre is nearest governs), bit-identical to vv_dsp_lpc_frames_device followed
+ * by vv_dsp_lpc_residual_device.  Zero frames: OK, nothing written. */
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpc_residual_device(const vv_dsp_real* d_x, size_t n, size_t nch,
+                                                          size_t x_stride, const vv_dsp_real* d_a, size_t order,
+                                                          size_t frames, size_t a_pitch, size_t a_ch_stride,
+                                                          const vv_dsp_real* d_gain, size_t g_ch_stride,
+                                                          size_t seg_len, long long offset, double* d_state,
+                                                          vv_dsp_real* d_e, size_t e_stride, void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpc_synth_device(const vv_dsp_real* d_e, size_t n, size_t nch, size_t e_stride,
+                                                       const vv_dsp_real* d_a, size_t order, size_t frames,
+                                                       size_t a_pitch, size_t a_ch_stride, const vv_dsp_real* d_gain,
+                                                       size_t g_ch_stride, size_t seg_len, long long offset,
+                                                       double* d_state, vv_dsp_real* d_y, size_t y_stride,
+                                                       void* stream);
+VV_DSP_NODISCARD vv_dsp_status vv_dsp_lpc_residual_frames_device(const vv_dsp_real* d_signal, size_t n, size_t nch,
+                                                                 size_t ch_stride, size_t frame_len, size_t hop_len,
+                                                                 int center, const vv_dsp_real* d_window, size_t order,
+                                                                 vv_dsp_real* d_a, size_t a_ch_stride,
+                                                                 vv_dsp_real* d_err, size_t err_ch_stride,
+                                                                 vv_dsp_real* d_e, size_t e_stride, void* stream);
 /* Array statistics (vv_dsp/core/stats.h, which states the numerics: the exact
  * class bit-identical to the reference, the f64 class within 1 ulp of it, one
  * summation order whatever the batch, stride, outputs or entry point).

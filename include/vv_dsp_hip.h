@@ -612,6 +612,31 @@ int vvhip_formants_frames_device(const float* d_signal, size_t n, size_t nch, si
 int vvhip_lpc_formants_host(const float* a, size_t order, const vvhip_formant_params* params,
                             const vvhip_formant_out* out);
 
+/* ---- LPC residual and synthesis filters (include/vv_dsp/envelope/lpc_filter.h;
+ * entry points as vv_dsp_amd.h's, `frames` per channel of the _frames_ call given
+ * by the caller) ----
+ * "STAT_LPC_RESIDUAL" / "STAT_LPC_SYNTH_EXACT" / "STAT_LPC_SYNTH_CHUNKED" count
+ * the calls of each route of lpc_filter_kernels.hip.  Knob LPC_SYNTH_CHUNK: 0
+ * never chunks, k > 0 forces chunks of k; knob LPC_FILTER_GROUP = g > 0 forces
+ * channel groups of g where scratch is taken per group (the chunked synthesis
+ * and the _frames_ call). */
+int vvhip_lpc_residual_device(const float* d_x, size_t n, size_t nch, size_t x_stride, const float* d_a, size_t order,
+                              size_t frames, size_t a_pitch, size_t a_ch_stride, const float* d_gain,
+                              size_t g_ch_stride, size_t seg_len, long long offset, double* d_state, float* d_e,
+                              size_t e_stride, void* stream);
+int vvhip_lpc_synth_device(const float* d_e, size_t n, size_t nch, size_t e_stride, const float* d_a, size_t order,
+                           size_t frames, size_t a_pitch, size_t a_ch_stride, const float* d_gain, size_t g_ch_stride,
+                           size_t seg_len, long long offset, double* d_state, float* d_y, size_t y_stride,
+                           void* stream);
+int vvhip_lpc_residual_frames_device(const float* d_signal, size_t n, size_t nch, size_t ch_stride, size_t frame_len,
+                                     size_t hop, size_t frames, int center, const float* d_window, size_t order,
+                                     float* d_a, size_t a_ch_stride, float* d_err, size_t err_ch_stride, float* d_e,
+                                     size_t e_stride, void* stream);
+int vvhip_lpc_residual_host(const float* x, size_t n, const float* a, size_t order, size_t frames, size_t seg_len,
+                            long long offset, const float* gain, double* state, float* e);
+int vvhip_lpc_synth_host(const float* e, size_t n, const float* a, size_t order, size_t frames, size_t seg_len,
+                         long long offset, const float* gain, double* state, float* y);
+
 /* ---- Spectral utilities (src/spectral/utils.c:5-73) ----
  * `batch` contiguous rows of n: fftshift (inverse 0) / ifftshift (inverse 1) of
  * float (cpx 0) or complex (cpx 1) rows, a permutation (in place allowed);

@@ -28,10 +28,10 @@ constexpr const char* KNOB_NAMES[KNOB_COUNT] = {
     "FS_VAR",        "FS_CHUNK_MB",  "FS_OLD",       "BLUE_UNFUSED", "C2C_MAX",    "STFT_SQ",
     "MIX_CHUNK_MB",  "MIX_R2C_FULL", "FIR_OLD",      "FIR_DYN",     "FIR_DIRECT_LDS", "FIR_BLOCK",
     "HOST_CHUNK_MB", "NO_MIXED",     "REAL_PROMOTE", "ISTFT_OLD",   "MEL_FUSED",   "CZT_UNFUSED",
-    "CEPS_UNFUSED",  "FIR_R32",      "DIST_SLAB_KB", "POW_R32", "MAG_R32",     "MEL_R32", "C2C_TPW", "C2C_ONE", "REAL_TPW", "ANA_TPW", "MIX_TPW", "C2C_SMALL", "DCT_SMALL", "HIL_SMALL", "REAL_SMALL", "R2C_SMALL", "STFT_STAGE", "STFT_ONE", "MFCC_WIN", "RESAMPLE_GENERIC", "LPC_GENERIC", "IIR_CHUNK", "STATS_LONG", "INTERP_ROWS", "PITCH_F32", "SHAPE_DWORD", "PVOC_GROUP", "PVOC_PLANE", "PTRACK_GROUP", "MEDIAN_SELECT", "HPSS_GROUP", "DENOISE_SEGMENT", "DENOISE_MIN", "DENOISE_GROUP", "LSF_GROUP",
+    "CEPS_UNFUSED",  "FIR_R32",      "DIST_SLAB_KB", "POW_R32", "MAG_R32",     "MEL_R32", "C2C_TPW", "C2C_ONE", "REAL_TPW", "ANA_TPW", "MIX_TPW", "C2C_SMALL", "DCT_SMALL", "HIL_SMALL", "REAL_SMALL", "R2C_SMALL", "STFT_STAGE", "STFT_ONE", "MFCC_WIN", "RESAMPLE_GENERIC", "LPC_GENERIC", "IIR_CHUNK", "STATS_LONG", "INTERP_ROWS", "PITCH_F32", "SHAPE_DWORD", "PVOC_GROUP", "PVOC_PLANE", "PTRACK_GROUP", "MEDIAN_SELECT", "HPSS_GROUP", "DENOISE_SEGMENT", "DENOISE_MIN", "DENOISE_GROUP", "LSF_GROUP", "LPC_SYNTH_CHUNK", "LPC_FILTER_GROUP",
 };
 constexpr const char* STAT_NAMES[STAT_COUNT] = {
-    "STAT_STFT_DYN", "STAT_FIR_DYN", "STAT_FIR_STATIC", "STAT_MEL_FUSED", "STAT_MEL_SPLIT", "STAT_FIR_R32", "STAT_POW_R32", "STAT_MAG_R32", "STAT_MEL_R32", "STAT_RESAMPLE_TABLE", "STAT_RESAMPLE_GENERIC", "STAT_LPC_WAVE", "STAT_LPC_GENERIC", "STAT_IIR_EXACT", "STAT_IIR_CHUNKED", "STAT_STATS_WAVE", "STAT_STATS_LONG", "STAT_INTERP_ONE", "STAT_INTERP_ROWS", "STAT_PITCH_WAVE", "STAT_SHAPE_WAVE", "STAT_SHAPE_VEC16", "STAT_PVOC_ROWS", "STAT_PITCH_TRACK", "STAT_DENOISE", "STAT_LSF", "STAT_FORMANT",
+    "STAT_STFT_DYN", "STAT_FIR_DYN", "STAT_FIR_STATIC", "STAT_MEL_FUSED", "STAT_MEL_SPLIT", "STAT_FIR_R32", "STAT_POW_R32", "STAT_MAG_R32", "STAT_MEL_R32", "STAT_RESAMPLE_TABLE", "STAT_RESAMPLE_GENERIC", "STAT_LPC_WAVE", "STAT_LPC_GENERIC", "STAT_IIR_EXACT", "STAT_IIR_CHUNKED", "STAT_STATS_WAVE", "STAT_STATS_LONG", "STAT_INTERP_ONE", "STAT_INTERP_ROWS", "STAT_PITCH_WAVE", "STAT_SHAPE_WAVE", "STAT_SHAPE_VEC16", "STAT_PVOC_ROWS", "STAT_PITCH_TRACK", "STAT_DENOISE", "STAT_LSF", "STAT_FORMANT", "STAT_LPC_RESIDUAL", "STAT_LPC_SYNTH_EXACT", "STAT_LPC_SYNTH_CHUNKED",
 };
 constexpr long long UNSET = -1;
 

@@ -241,7 +241,7 @@ private:
         void* down;   // host destination of finish(), or null
         size_t bytes;
     };
-    static constexpr int MAX_BUFS = 4;
+    static constexpr int MAX_BUFS = 6;
     const char* what;
     Buf bufs[MAX_BUFS];
     int nbuf = 0;

@@ -18,11 +18,11 @@ enum Knob : int {
     KNOB_MIX_CHUNK_MB, KNOB_MIX_R2C_FULL, KNOB_FIR_OLD, KNOB_FIR_DYN, KNOB_FIR_DIRECT_LDS, KNOB_FIR_BLOCK,
     KNOB_HOST_CHUNK_MB, KNOB_NO_MIXED, KNOB_REAL_PROMOTE, KNOB_ISTFT_OLD, KNOB_MEL_FUSED, KNOB_CZT_UNFUSED,
     KNOB_CEPS_UNFUSED, KNOB_FIR_R32, KNOB_DIST_SLAB_KB, KNOB_POW_R32, KNOB_MAG_R32, KNOB_MEL_R32,
-    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_SHAPE_DWORD, KNOB_PVOC_GROUP, KNOB_PVOC_PLANE, KNOB_PTRACK_GROUP, KNOB_MEDIAN_SELECT, KNOB_HPSS_GROUP, KNOB_DENOISE_SEGMENT, KNOB_DENOISE_MIN, KNOB_DENOISE_GROUP, KNOB_LSF_GROUP, KNOB_COUNT
+    KNOB_C2C_TPW, KNOB_C2C_ONE, KNOB_REAL_TPW, KNOB_ANA_TPW, KNOB_MIX_TPW, KNOB_C2C_SMALL, KNOB_DCT_SMALL, KNOB_HIL_SMALL, KNOB_REAL_SMALL, KNOB_R2C_SMALL, KNOB_STFT_STAGE, KNOB_STFT_ONE, KNOB_MFCC_WIN, KNOB_RESAMPLE_GENERIC, KNOB_LPC_GENERIC, KNOB_IIR_CHUNK, KNOB_STATS_LONG, KNOB_INTERP_ROWS, KNOB_PITCH_F32, KNOB_SHAPE_DWORD, KNOB_PVOC_GROUP, KNOB_PVOC_PLANE, KNOB_PTRACK_GROUP, KNOB_MEDIAN_SELECT, KNOB_HPSS_GROUP, KNOB_DENOISE_SEGMENT, KNOB_DENOISE_MIN, KNOB_DENOISE_GROUP, KNOB_LSF_GROUP, KNOB_LPC_SYNTH_CHUNK, KNOB_LPC_FILTER_GROUP, KNOB_COUNT
 };
 long long knob(Knob k, long long dflt);
 // launches of the paths the tests must see taken (vvhip_debug_get("STAT_..."))
-enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_PITCH_WAVE, STAT_SHAPE_WAVE, STAT_SHAPE_VEC16, STAT_PVOC_ROWS, STAT_PITCH_TRACK, STAT_DENOISE, STAT_LSF, STAT_FORMANT, STAT_COUNT };
+enum Stat : int { STAT_STFT_DYN, STAT_FIR_DYN, STAT_FIR_STATIC, STAT_MEL_FUSED, STAT_MEL_SPLIT, STAT_FIR_R32, STAT_POW_R32, STAT_MAG_R32, STAT_MEL_R32, STAT_RESAMPLE_TABLE, STAT_RESAMPLE_GENERIC, STAT_LPC_WAVE, STAT_LPC_GENERIC, STAT_IIR_EXACT, STAT_IIR_CHUNKED, STAT_STATS_WAVE, STAT_STATS_LONG, STAT_INTERP_ONE, STAT_INTERP_ROWS, STAT_PITCH_WAVE, STAT_SHAPE_WAVE, STAT_SHAPE_VEC16, STAT_PVOC_ROWS, STAT_PITCH_TRACK, STAT_DENOISE, STAT_LSF, STAT_FORMANT, STAT_LPC_RESIDUAL, STAT_LPC_SYNTH_EXACT, STAT_LPC_SYNTH_CHUNKED, STAT_COUNT };
 void stat_inc(Stat s);
 
 // Device-resident W_N^k = exp(-2*pi*i*k/N) table, k < N, f32 rounded from double.
@@ -466,6 +466,40 @@ struct FormantOut {
 // per root, 8 / 4 / 2 rows per wave for orders up to 8 / 16 / 32.
 hipError_t launch_formants(const float* a, int order, long long rows, long long a_pitch, const FormantCfg& cfg,
                            const FormantOut& out, hipStream_t s);
+
+// ---- LPC residual and synthesis filters (lpc_filter_kernels.hip),
+// include/vv_dsp/envelope/lpc_filter.h ----
+constexpr int LPCF_MAX_ORDER = 32;                // VV_DSP_LPC_FILTER_MAX_ORDER
+constexpr long long LPCF_EXACT_MAX = 8192;        // VV_DSP_LPC_SYNTH_EXACT_MAX
+constexpr long long LPCF_CHUNK = 1024;            // VV_DSP_LPC_SYNTH_CHUNK
+constexpr int LPCF_TILE = 1024;                   // samples of a channel per workgroup of the residual
+// The signal [rows][n] and what governs it: row r reads coefficient rows
+// a + r * a_ch_stride + f * a_pitch and gains gain + r * g_ch_stride + f (gain
+// null: 1), f = clamp((t + offset) / seg_len, 0, frames - 1); state [rows][order]
+// doubles, null: zeros in and nothing out.
+struct LpcFilt {
+    const float* x = nullptr;
+    float* y = nullptr;
+    long long n = 0, rows = 0, x_stride = 0, y_stride = 0;
+    const float* a = nullptr;
+    const float* gain = nullptr;
+    long long frames = 0, a_pitch = 0, a_ch_stride = 0, g_ch_stride = 0, seg_len = 1, offset = 0;
+    int order = 0;
+    double* state = nullptr;
+};
+// residual: one workgroup per tile of LPCF_TILE samples of a row, then the state update
+hipError_t launch_lpc_residual(const LpcFilt& f, hipStream_t s);
+// The synthesis walk over rows * chunks sub-rows, one lane each: sub-row q = row *
+// chunks + c is samples [c L, min(n, (c + 1) L)) and starts from zin[q * order + ..]
+// (zin null: from f.state[row], chunks == 1); the last sub-row of a row leaves its
+// end state in f.state[row].  This is the header's recursion, bit for bit.
+hipError_t launch_lpc_synth_walk(const LpcFilt& f, long long chunks, long long L, const double* zin, hipStream_t s);
+// per sub-row: the end state from zero state, z [q][order], and the transition
+// phi [q][order (unit state i)][order (component r)]; one wave per sub-row
+hipError_t launch_lpc_synth_phi(const LpcFilt& f, long long chunks, long long L, double* phi, double* z, hipStream_t s);
+// per row: s_0 = f.state[row] (null: 0), s_{c+1} = phi_c s_c + z_c; zin[q][order] = s_c
+hipError_t launch_lpc_synth_scan(const LpcFilt& f, long long chunks, const double* phi, const double* z, double* zin,
+                                 hipStream_t s);
 
 // ---- per-frame spectral shape (shape_kernels.hip), include/vv_dsp/features/spectral_shape.h ----
 constexpr int SHAPE_MAX_BINS = 8193;             // K = n_fft / 2 + 1 of a row

@@ -85,6 +85,7 @@ LSF_NAMES = ("lsf", "rc", "flags")
 LSF_STABLE, LSF_COMPLETE = 1, 2          # bits of the lsf flags word
 FORMANT_CONVERGED = 1                    # bit of the formant flags word
 LSF_MAX_ORDER = 32
+LPC_FILTER_MAX_ORDER = 32
 
 
 class SpectralShapeParams(C.Structure):
@@ -232,6 +233,12 @@ def lib():
     L.vv_dsp_lsf_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
     L.vv_dsp_lpc_to_lsf.argtypes = [_vp, _sz, _vp, _vp, _vp]
     L.vv_dsp_lsf_to_lpc.argtypes = [_vp, _sz, _vp]
+    for f in ("residual", "synth"):
+        getattr(L, f"vv_dsp_lpc_{f}_device").argtypes = [_vp, _sz, _sz, _sz, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _sz,
+                                                         C.c_longlong, _vp, _vp, _sz, _vp]
+        getattr(L, f"vv_dsp_lpc_{f}").argtypes = [_vp, _sz, _vp, _sz, _sz, _sz, C.c_longlong, _vp, _vp, _vp]
+    L.vv_dsp_lpc_residual_frames_device.argtypes = [_vp, _sz, _sz, _sz, _sz, _sz, C.c_int, _vp, _sz, _vp, _sz, _vp,
+                                                    _sz, _vp, _sz, _vp]
     L.vv_dsp_formant_params_default.argtypes = [C.c_float, C.POINTER(FormantParams)]
     L.vv_dsp_formant_start_points.argtypes = [_sz, _vp]
     L.vv_dsp_lpc_formants.argtypes = [_vp, _sz, C.POINTER(FormantParams), C.POINTER(FormantOut)]
@@ -1071,6 +1078,111 @@ def lsf_frames(sig, frame_len, hop, order, what=LSF_NAMES + ("err",), window=Non
                                               _opt(planes, "flags"), _opt(planes, "err"), _stream(stream)),
                "lsf_frames_device")
     return _planes_of(planes, sig)
+
+
+def _lpc_filter(which, x, a, seg_len, offset, gain, state, out, stream):
+    who = f"lpc_{which}"
+    x2 = _strided_rows(x, f"{who} input")
+    nch, n = x2.shape
+    if a.dim() not in (2, 3) or a.dtype != torch.float32 or not a.is_cuda or a.numel() == 0 or a.stride(-1) != 1 \
+            or (a.dim() == 3 and a.shape[0] != nch):
+        raise VvError(f"{who} rows: float32 device rows (frames, order + 1), or (nch, frames, order + 1) with "
+                      f"nch = {nch}, with unit coefficient stride")
+    frames, w = a.shape[-2:]
+    order = w - 1
+    if order < 1 or order > LPC_FILTER_MAX_ORDER or seg_len < 1:
+        raise VvError(f"{who}: order {order} (1..{LPC_FILTER_MAX_ORDER}), seg_len {seg_len}")
+    pitch = a.stride(-2) if frames > 1 else max(w, a.stride(-2))
+    a_ch = 0 if a.dim() == 2 else a.stride(0) if nch > 1 else max(a.stride(0), (frames - 1) * pitch + w)
+    if pitch < w or (a_ch and a_ch < (frames - 1) * pitch + w):
+        raise VvError(f"{who} rows: overlapping rows")
+    g_ch = 0
+    if gain is not None:
+        if gain.dim() not in (1, 2) or gain.dtype != torch.float32 or not gain.is_cuda or gain.shape[-1] != frames \
+                or (frames > 1 and gain.stride(-1) != 1) or (gain.dim() == 2 and gain.shape[0] != nch):
+            raise VvError(f"{who} gain: float32 device tensor ({frames},) or ({nch}, {frames}) with unit stride "
+                          f"along the frames")
+        g_ch = 0 if gain.dim() == 1 else gain.stride(0) if nch > 1 else max(frames, gain.stride(0))
+        if g_ch and g_ch < frames:
+            raise VvError(f"{who} gain: overlapping rows")
+    if state is not None:
+        _expect(state, torch.float64, nch * order, f"{who} state")
+        if state.numel() != nch * order:
+            raise VvError(f"{who} state: ({nch}, {order}) float64")
+    y = torch.empty((nch, n), dtype=torch.float32, device=x.device) if out is None else out
+    y2 = _strided_rows(y, f"{who} output")
+    if tuple(y2.shape) != (nch, n):
+        raise VvError(f"{who} output: shape {tuple(y2.shape)}, expected {(nch, n)}")
+    if n and nch:
+        fn = getattr(lib(), f"vv_dsp_lpc_{which}_device")
+        _check(fn(_vp(x2.data_ptr()), n, nch, x2.stride(0) if nch > 1 else n, _vp(a.data_ptr()), order, frames, pitch,
+                  a_ch, None if gain is None else _vp(gain.data_ptr()), g_ch, int(seg_len), int(offset),
+                  None if state is None else _vp(state.data_ptr()), _vp(y2.data_ptr()),
+                  y2.stride(0) if nch > 1 else n, _stream(stream)), f"{who}_device")
+    return y if out is not None or x.dim() == 2 else y[0]
+
+
+def lpc_residual(x, a, seg_len, offset=0, gain=None, state=None, out=None, stream=None):
+    """The time-varying inverse filter A(z) (vv_dsp/envelope/lpc_filter.h): x (nch, n) or (n,)
+    float32 rows, which may be x.stride(0) floats apart -> e of the same shape.  a: LPC rows
+    (frames, order + 1) shared by every channel or (nch, frames, order + 1), A(z) = 1 + sum a[m]
+    z^-m, rows a.stride(-2) floats apart (the rows of lpc_frames and lsf_to_lpc as they are).
+    Sample t is governed by row clamp((t + offset) // seg_len, 0, frames - 1).  gain: (frames,) or
+    (nch, frames) float32 (rows gain.stride(0) apart), e is divided by it; state: (nch, order) float64, the inputs before
+    sample 0 newest first, updated in place (None: zeros).  Bit-identical to the header's f64
+    arithmetic.  out may not overlap x."""
+    return _lpc_filter("residual", x, a, seg_len, offset, gain, state, out, stream)
+
+
+def lpc_synth(e, a, seg_len, offset=0, gain=None, state=None, out=None, stream=None):
+    """The time-varying all-pole filter g / A(z), the inverse of lpc_residual with the same
+    arguments: e (nch, n) or (n,) -> y.  The state holds the f64 outputs before sample 0.  Rows up
+    to 8192 samples are one recursion, bit-identical to the header; longer rows are chunked with
+    the chunks' states carried in f64.  out may be e."""
+    return _lpc_filter("synth", e, a, seg_len, offset, gain, state, out, stream)
+
+
+def lpc_residual_frames(sig, frame_len, hop, order, window=None, center=False, what=("e",), stream=None):
+    """Signal (nch, n) or (n,) float32 -> {name: tensor} for the names in `what`: "e" the residual
+    of the signal through its own per-frame LPC rows, (nch, n); "a" the rows (nch, frames, order +
+    1); "err" (nch, frames).  lpc_frames followed by lpc_residual with seg_len = hop and the
+    offset that lets the frame with the nearest centre govern, bit-identical to the two calls;
+    rows that are not asked for stay in scratch (vv_dsp_lpc_residual_frames_device)."""
+    sig2, nch, n = _signal(sig, "lpc_residual_frames")
+    what = _named(what, ("e", "a", "err"), "lpc_residual_frames")
+    if frame_len <= 0 or hop <= 0 or order < 1 or order > LPC_FILTER_MAX_ORDER or order + 1 > frame_len:
+        raise VvError(f"lpc_residual_frames: frame_len {frame_len}, hop {hop}, order {order}")
+    win = _window(window, frame_len, "lpc_residual_frames")
+    fr = num_frames(n, frame_len, hop, center)
+    planes = {"e": torch.empty((nch, n), dtype=torch.float32, device=sig.device)}
+    if "a" in what:
+        planes["a"] = torch.empty((nch, fr, order + 1), dtype=torch.float32, device=sig.device)
+    if "err" in what:
+        planes["err"] = torch.empty((nch, fr), dtype=torch.float32, device=sig.device)
+    if fr and nch and n:
+        _check(lib().vv_dsp_lpc_residual_frames_device(_vp(sig2.data_ptr()), n, nch, max(sig2.stride(0), n),
+                                                       frame_len, hop, int(bool(center)), win, order,
+                                                       _opt(planes, "a"), fr * (order + 1), _opt(planes, "err"), fr,
+                                                       _vp(planes["e"].data_ptr()), n, _stream(stream)),
+               "lpc_residual_frames_device")
+    return _planes_of({k: planes[k] for k in what}, sig)
+
+
+def pitch_shift_lpc(sig, ratio, frame_len, hop, order, n_fft, stft_hop, window=None):
+    """Pitch shift by `ratio` with the formants kept (the chain of INTEGRATION.md): the residual
+    of sig (nch, n) or (n,) through its own centred LPC rows, time-stretched to `ratio` times its
+    length by the phase vocoder (Stft(n_fft, stft_hop).time_stretch at rate 1 / ratio), read back
+    at step `ratio` (cubic) to n samples, and synthesised through the original rows.  A pure
+    composition of lpc_residual_frames, Stft.time_stretch, interpolate_uniform and lpc_synth."""
+    if not ratio > 0:
+        raise VvError(f"pitch_shift_lpc: ratio {ratio}")
+    sig2, nch, n = _signal(sig, "pitch_shift_lpc")
+    r = lpc_residual_frames(sig2, frame_len, hop, order, window=window, center=True, what=("e", "a"))
+    st = Stft(n_fft, stft_hop)
+    long = st.time_stretch(r["e"], 1.0 / float(ratio))
+    e2 = interpolate_uniform(long, 0.0, float(ratio), n, method="cubic")
+    y = lpc_synth(e2, r["a"], hop, hop // 2)
+    return y if sig.dim() == 2 else y[0]
 
 
 def formant_params(sample_rate, **fields):
